@@ -17,6 +17,13 @@ every rank all 80 layers (full replication, DP-serving placement). Each GPU
 therefore receives 80 GiB into HBM per step at every N: at N = 1 all of it
 crosses PCIe; at N = 8, 10 GiB per GPU crosses PCIe and 70 GiB arrives over
 xGMI. value = N x 80 GiB / step time (GB/s, 1e9 bytes).
+
+A plain run sets up, warms up, times the K steps and prints the result line;
+nothing else is measured. ``--dump-outputs DIR`` also writes what the last timed
+step left in rank 0's HBM (dump_outputs below). ``--full`` is where secondary
+measurements belong (other precisions or sizes, baselines, per-kernel figures
+that take runs of their own); the benchmark has none today, so the option
+changes nothing yet.
 """
 
 from __future__ import annotations
@@ -31,6 +38,8 @@ import time
 HERE = os.path.dirname(os.path.abspath(__file__))
 BASELINE_METRIC = "aggregate GB/s + time-to-full-placement, 80×1 GiB layers, mode 1, 8 ranks"
 PROBE_BYTES = 4 << 30  # node NVMe probe file (N > 1, --tier disk): past typical drive caches
+DUMP_SAMPLE_BYTES = 12 << 20  # --dump-outputs: sampled bytes in all (one float32 each: 48 MiB of .npy)
+DUMP_BLOCK = 4096  # --dump-outputs: bytes per sampled range of a layer larger than its share
 
 
 def metric_name(layers: int, layer_mib: int, mode: int, ranks: int) -> str:
@@ -41,11 +50,72 @@ def metric_name(layers: int, layer_mib: int, mode: int, ranks: int) -> str:
             f"{ranks} rank{'s' if ranks != 1 else ''}")
 
 
+def dump_plan(sizes, budget: int = DUMP_SAMPLE_BYTES, block: int = DUMP_BLOCK, seed: int = 0):
+    """The byte ranges of every layer that --dump-outputs writes: [(layer, offset,
+    length)], the same for the same sizes. A layer within its share of `budget`
+    is taken whole; of a larger one the first and the last `block` bytes and
+    seeded random blocks in between, in offset order, at most its share."""
+    import numpy as np
+
+    rng = np.random.RandomState(seed)
+    share = max(2 * block, budget // max(1, len(sizes)) // block * block)
+    plan = []
+    for layer, n in enumerate(sizes):
+        if n <= share:
+            plan.append((layer, 0, n))
+            continue
+        inner = rng.randint(0, n - block + 1, size=share // block - 2)
+        for off in sorted({0, n - block, *(int(o) for o in inner)}):
+            plan.append((layer, off, block))
+    return plan
+
+
+def dump_outputs(path: str, rt, _core) -> None:
+    """--dump-outputs: what the last timed step left in this rank's HBM, the
+    layers a caller of the timed path holds afterwards, as DIR/<name>.npy:
+
+      layers_crc32c.npy        float64 [chunks]: CRC32C of every chunk of every layer (layer-major,
+                               on the engine's chunk grid), computed on the GPU over the whole output
+      layers_sample.npy        float32 [bytes]: the byte ranges of dump_plan(), end to end, one value per byte
+      layers_sample_index.npy  float64 [ranges, 3]: layer, byte offset and length of each range
+      layers_unpacked_*.npy    the same two of the dequantized bf16 images (--pack fp8 --store bf16)
+
+    The sample is fixed (seeded) and bounded: DUMP_SAMPLE_BYTES bytes in all."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    layers = sorted(rt.sizes)
+    images = [("layers", False)] + ([("layers_unpacked", True)] if rt.pack == "fp8" and rt.store == "bf16" else [])
+    crcs = []
+    for name, unpacked in images:
+        views = [rt.layer_tensor(l, unpacked=unpacked) for l in layers]
+        plan = dump_plan([v.numel() for v in views], DUMP_SAMPLE_BYTES // len(images))
+        parts = []
+        for i, off, n in plan:
+            parts.append(views[i][off:off + n].to(torch.float32).cpu().numpy())
+        np.save(os.path.join(path, f"{name}_sample.npy"), np.concatenate(parts) if parts else np.zeros(0, np.float32))
+        np.save(os.path.join(path, f"{name}_sample_index.npy"),
+                np.array([(layers[i], off, n) for i, off, n in plan], dtype=np.float64).reshape(-1, 3))
+        if not unpacked:
+            for v in views:
+                crcs.extend(_core.crc32c_chunks(v.data_ptr(), v.numel(), rt.grid))
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, "layers_crc32c.npy"), np.array(crcs, dtype=np.float64))
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--gpus", type=int, default=None, help="ranks (default: WORLD_SIZE or 1)")
     p.add_argument("--steps", type=int, default=5, help="timed sessions")
     p.add_argument("--warmup", type=int, default=1, help="untimed sessions first")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last one left in rank 0's HBM as DIR/<name>.npy: the "
+                        "CRC32C of every chunk and a fixed, seeded sample of the bytes (dump_outputs); the inputs "
+                        "are seeded, so two builds run with the same arguments compare file for file")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (anything beyond the headline figure belongs "
+                        "behind this option); there are none today")
     p.add_argument("--mode", type=int, default=1, choices=[0, 1, 2, 3],
                    help="distribution mode (BASELINE config #3: 1, peer retransmission)")
     p.add_argument("--layers", type=int, default=80, help="layers (config #3: 80)")
@@ -423,6 +493,13 @@ def worker(args, world, rank, chan) -> int:
         disk_bytes["buffered"] += last.engine_stats.get("disk_buffered_bytes", 0)
         log(f"step {i}: {dt * 1e3:.1f} ms ({total_bytes / dt / 1e9:.1f} GB/s) ttd={last.time_to_deliver_s * 1e3:.1f} ms")
     beat("measured")
+    if args.dump_outputs and rank == 0:
+        if last is None:
+            failed("--dump-outputs needs at least one timed step")
+        beat("dump outputs")
+        t_dump = time.time()
+        dump_outputs(args.dump_outputs, rt, _core)
+        log(f"outputs written to {args.dump_outputs} in {time.time() - t_dump:.1f}s")
     if args.tier == "disk":
         if world > 1:
             got = [None] * world
