@@ -8,6 +8,7 @@
 
 #include "core/crc32c.h"
 #include "core/fp8.h"
+#include "core/mxfp4.h"
 #include "core/log.h"
 #include "core/ratelimit.h"
 #include "core/trace.h"
@@ -545,6 +546,38 @@ PYBIND11_MODULE(_core, m) {
     }
     return py::bytes(out);
   }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block") = 128);
+  // MXFP4 wire/storage format (core/mxfp4.h), host reference
+  m.def("mxfp4_packed_size", &mxfp4::packed_size, py::arg("src_bytes"), py::arg("src_chunk"));
+  m.def("mxfp4_source_size", &mxfp4::source_size, py::arg("packed"), py::arg("src_chunk"));
+  m.def("mxfp4_pack_layer_host", [](py::bytes src, int64_t src_chunk) {
+    std::string s(src);
+    mxfp4::check(int64_t(s.size()), src_chunk);
+    std::string out(size_t(mxfp4::packed_size(int64_t(s.size()), src_chunk)), '\0');
+    {
+      py::gil_scoped_release nogil;
+      mxfp4::pack_layer_host(reinterpret_cast<const uint8_t*>(s.data()), int64_t(s.size()), src_chunk,
+                             reinterpret_cast<uint8_t*>(out.data()));
+    }
+    return py::bytes(out);
+  }, py::arg("src"), py::arg("src_chunk"));
+  m.def("mxfp4_pack_layer_into", [](uint64_t src, int64_t src_bytes, int64_t src_chunk, uint64_t dst) {
+    py::gil_scoped_release nogil;
+    mxfp4::pack_layer_host(reinterpret_cast<const uint8_t*>(src), src_bytes, src_chunk,
+                           reinterpret_cast<uint8_t*>(dst));
+  });
+  m.def("mxfp4_unpack_layer_host", [](py::bytes packed, int64_t src_bytes, int64_t src_chunk) {
+    std::string s(packed);
+    mxfp4::check(src_bytes, src_chunk);
+    if (int64_t(s.size()) != mxfp4::packed_size(src_bytes, src_chunk))
+      throw std::runtime_error("packed buffer size does not match src_bytes");
+    std::string out(size_t(src_bytes), '\0');
+    {
+      py::gil_scoped_release nogil;
+      mxfp4::unpack_layer_host(reinterpret_cast<const uint8_t*>(s.data()), src_bytes, src_chunk,
+                               reinterpret_cast<uint8_t*>(out.data()));
+    }
+    return py::bytes(out);
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"));
 
   // ---- roles
   py::class_<NodeConfig>(m, "NodeConfig")

@@ -32,6 +32,9 @@ namespace dissem {
 
 using Ev = uint64_t;  // 0 = no event
 
+// Packed wire/storage formats (PlannedConfig::pack): core/fp8.h, core/mxfp4.h.
+constexpr int kPackFp8 = 1, kPackMxfp4 = 2;
+
 struct XOp {
   bool send;
   int peer;  // partner rank; the root rank when bcast
@@ -53,9 +56,10 @@ class Backend {
   virtual void free_host(uint8_t* p) = 0;
   // copy queue: async host -> device copy; event fires when it landed
   virtual Ev stage(uint8_t* dst, const uint8_t* src_host, int64_t n) = 0;
-  // copy queue: host -> device copy of `n_src` bytes of bf16, then fp8-pack them
-  // into dst in the packed chunk layout of core/fp8.h
-  virtual Ev stage_pack(uint8_t* dst, const uint8_t* src_host, int64_t n_src, int block) = 0;
+  // copy queue: host -> device copy of `n_src` bytes of bf16, then pack them
+  // into dst in the packed chunk layout of `format` (core/fp8.h with `block`
+  // elements per scale, or core/mxfp4.h, whose block is 32)
+  virtual Ev stage_pack(uint8_t* dst, const uint8_t* src_host, int64_t n_src, int block, int format = kPackFp8) = 0;
   // Independent comm lanes (>= 1).
   virtual int lanes() const { return 1; }
   // comm lane `lane`: wait for `waits`, then one grouped set of P2P sends/recvs
@@ -74,10 +78,10 @@ class Backend {
   // verify queue: wait for `waits`, then check every request - all of them in
   // one event (one launch per kCrcBatchMax requests on GPUs, the fold inside
   // it): the CRC32C of [p, p+n) into result slot `slot`. A request with `out`
-  // is an fp8-packed chunk (core/fp8.h layout of `n` bf16 SOURCE bytes with
-  // `block`-element scales): its packed bytes are checked and dequantized to
-  // `out` in the same pass (the fused kernel). No requests: an ordering
-  // marker on the verify queue.
+  // is a packed chunk (`format`: the core/fp8.h layout of `n` bf16 SOURCE bytes
+  // with `block`-element scales, or the core/mxfp4.h one): its packed bytes are
+  // checked and dequantized to `out` in the same pass (the fused kernel). No
+  // requests: an ordering marker on the verify queue.
   struct CheckReq {
     const uint8_t* p;
     int64_t n;
@@ -87,6 +91,7 @@ class Backend {
     // The CRC the engine expects. Only the timing-only simulator uses it
     // (SimTiming::copy_bytes false moves no bytes, so it reports this value).
     uint32_t expect = 0;
+    int format = kPackFp8;
   };
   virtual Ev verify(const std::vector<CheckReq>& reqs, const std::vector<Ev>& waits) = 0;
   virtual int query(Ev e) = 0;  // 1 done, 0 pending, -1 failed

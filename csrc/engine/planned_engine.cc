@@ -38,6 +38,7 @@
 #include <set>
 
 #include "core/fp8.h"
+#include "core/mxfp4.h"
 #include "core/log.h"
 #include "core/queue.h"
 #include "core/trace.h"
@@ -78,10 +79,14 @@ PlannedEngine::PlannedEngine(const PlannedConfig& cfg, std::unique_ptr<Backend> 
   if (cfg_.pack == 1) {
     fp8::check(cfg_.chunk_bytes, cfg_.chunk_bytes, cfg_.pack_block);
     grid_ = fp8::packed_chunk(cfg_.chunk_bytes, cfg_.pack_block);
+  } else if (cfg_.pack == kPackMxfp4) {
+    cfg_.pack_block = mxfp4::kBlock;
+    mxfp4::check(cfg_.chunk_bytes, cfg_.chunk_bytes);
+    grid_ = mxfp4::packed_chunk(cfg_.chunk_bytes);
   } else if (cfg_.pack != 0) {
     throw std::runtime_error("unknown pack format " + std::to_string(cfg_.pack));
   }
-  if (cfg_.unpack_store && cfg_.pack != 1) throw std::runtime_error("unpack_store needs pack = fp8");
+  if (cfg_.unpack_store && cfg_.pack == 0) throw std::runtime_error("unpack_store needs pack = fp8 or mxfp4");
   inject_rng_.seed(cfg_.inject_seed * 0x9E3779B97F4A7C15ull + uint64_t(cfg_.rank));
   lanes_ = std::max(1, backend_->lanes());
   ops_.resize(size_t(lanes_));
@@ -193,12 +198,21 @@ int64_t PlannedEngine::slot_size(int64_t src_bytes) const {
     fp8::check(src_bytes, cfg_.chunk_bytes, cfg_.pack_block);
     return fp8::packed_size(src_bytes, cfg_.chunk_bytes, cfg_.pack_block);
   }
+  if (cfg_.pack == kPackMxfp4) {
+    mxfp4::check(src_bytes, cfg_.chunk_bytes);
+    return mxfp4::packed_size(src_bytes, cfg_.chunk_bytes);
+  }
   return src_bytes;
 }
 
+int64_t PlannedEngine::source_size(int64_t packed) const {
+  return cfg_.pack == kPackMxfp4 ? mxfp4::source_size(packed, cfg_.chunk_bytes)
+                                 : fp8::source_size(packed, cfg_.chunk_bytes, cfg_.pack_block);
+}
+
 int64_t PlannedEngine::src_len(const Layer& L, int64_t c) const {
-  if (cfg_.pack == 1 && !L.src_packed) {
-    const int64_t src = fp8::source_size(L.size, cfg_.chunk_bytes, cfg_.pack_block);
+  if (cfg_.pack != 0 && !L.src_packed) {
+    const int64_t src = source_size(L.size);
     return std::min(cfg_.chunk_bytes, src - c * cfg_.chunk_bytes);
   }
   return std::min(grid_, L.size - c * grid_);
@@ -220,7 +234,7 @@ PlannedEngine::Layer& PlannedEngine::layer(LayerID id, int64_t size_hint) {
 
 uint8_t* PlannedEngine::provision(LayerID id, int64_t size) {
   std::lock_guard<std::mutex> lk(req_mu_);  // setup runs while the issue thread is idle
-  if (cfg_.pack == 1) (void)fp8::source_size(size, cfg_.chunk_bytes, cfg_.pack_block);  // must be a packed size
+  if (cfg_.pack != 0) (void)source_size(size);  // must be a packed size
   Layer& L = layer(id, size);
   if (L.size != size) throw std::runtime_error("layer " + std::to_string(id) + " re-provisioned with another size");
   if (!L.dev) L.dev = backend_->alloc(size);

@@ -86,9 +86,9 @@ struct PlannedConfig {
   // fp8 wire/storage format (core/fp8.h): layers are staged from bf16 sources
   // and packed on the copy queue; HBM slots, transfers and CRCs use the packed
   // chunk grid. chunk_bytes stays the SOURCE (bf16) chunk.
-  int pack = 0;                    // 0 none, 1 fp8 e4m3fn block-scaled
-  int pack_block = 128;            // elements per f32 scale
-  // pack = fp8 only: every chunk that becomes resident (received or staged) is
+  int pack = 0;                    // 0 none, 1 fp8 e4m3fn block-scaled, 2 MXFP4 (core/mxfp4.h)
+  int pack_block = 128;            // elements per scale (MXFP4: forced to 32)
+  // pack != 0 only: every chunk that becomes resident (received or staged) is
   // also dequantized to bf16 into a second HBM slot of the layer by the fused
   // verify+unpack kernel - the CRC check and the dequantization in one pass
   // over the packed bytes (--store bf16). Every rank then holds the same bf16
@@ -408,10 +408,12 @@ class PlannedEngine : public DataEngine {
   void drop_pending_checks();
   void fail(const std::string& what);
   int64_t src_len(const Layer& L, int64_t c) const;  // source bytes of chunk c
-  int64_t src_grid(const Layer& L) const { return cfg_.pack == 1 && !L.src_packed ? cfg_.chunk_bytes : grid_; }
+  int64_t src_grid(const Layer& L) const { return cfg_.pack != 0 && !L.src_packed ? cfg_.chunk_bytes : grid_; }
+  // bf16 bytes of a layer whose packed size is `packed` (throws if it is no packed size)
+  int64_t source_size(int64_t packed) const;
 
   PlannedConfig cfg_;
-  int64_t grid_ = 0;  // chunk grid of HBM slots and transfers (packed chunk with pack=fp8)
+  int64_t grid_ = 0;  // chunk grid of HBM slots and transfers (the packed chunk with pack != 0)
   std::mt19937_64 inject_rng_;
   std::unique_ptr<Backend> backend_;
   NodeID self_node_ = 0;

@@ -41,10 +41,12 @@ bool PlannedEngine::stage_paced(Layer& L, LayerID id, int64_t c) {
 }
 
 Backend::CheckReq PlannedEngine::unpack_req(Layer& L, int64_t c, uint32_t slot) {
-  const int64_t src_total = fp8::source_size(L.size, cfg_.chunk_bytes, cfg_.pack_block);
+  const int64_t src_total = source_size(L.size);
   if (!L.out) L.out = backend_->alloc(src_total);
   const int64_t slen = std::min(cfg_.chunk_bytes, src_total - c * cfg_.chunk_bytes);
-  return Backend::CheckReq{L.dev + c * grid_, slen, slot, L.out + c * cfg_.chunk_bytes, cfg_.pack_block};
+  Backend::CheckReq r{L.dev + c * grid_, slen, slot, L.out + c * cfg_.chunk_bytes, cfg_.pack_block};
+  r.format = cfg_.pack;
+  return r;
 }
 
 void PlannedEngine::partial_landed(Layer& L, const Piece& p, std::vector<Verify>& out) {
@@ -277,7 +279,7 @@ void PlannedEngine::stage_from(Layer& L, LayerID id, int64_t c, const uint8_t* s
   const int64_t slen = src_len(L, c);
   trace::Scoped tr("dissem.stage");
   if (!L.dev) L.dev = backend_->alloc(L.size);
-  Ev e = cfg_.pack == 1 && !L.src_packed ? backend_->stage_pack(L.dev + off, src, slen, cfg_.pack_block)
+  Ev e = cfg_.pack != 0 && !L.src_packed ? backend_->stage_pack(L.dev + off, src, slen, cfg_.pack_block, cfg_.pack)
                                          : backend_->stage(L.dev + off, src, len);
   L.st[size_t(c)] = 1;
   L.rkey[size_t(c)] = Key{};

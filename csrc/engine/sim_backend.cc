@@ -34,6 +34,7 @@
 
 #include "core/crc32c.h"
 #include "core/fp8.h"
+#include "core/mxfp4.h"
 #include "core/queue.h"
 #include "core/vclock.h"
 #include "engine/backend.h"
@@ -341,13 +342,14 @@ class SimBackend : public Backend {
     return id;
   }
 
-  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block) override {
+  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block, int format) override {
     auto [id, ev] = make_event();
     const bool copy = fab_->timing.copy_bytes;
     copy_.push([=] {
       const double t0 = vclock::now();
       const int64_t n = n_src / 2;
-      if (copy) fp8::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, reinterpret_cast<float*>(dst + n), block);
+      if (copy && format == kPackMxfp4) mxfp4::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, dst + n / 2);
+      else if (copy) fp8::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, reinterpret_cast<float*>(dst + n), block);
       stage_delay(t0, n_src);
       ev->set(1);
     });
@@ -471,6 +473,10 @@ class SimBackend : public Backend {
     return ev && ev->state.load() > 0 ? ev->ms : -1;
   }
 
+  static int64_t packed_len(const CheckReq& r) {  // packed bytes of a fused request
+    return r.format == kPackMxfp4 ? mxfp4::packed_len(r.n) : fp8::packed_len(r.n, r.block);
+  }
+
   Ev verify(const std::vector<CheckReq>& reqs, const std::vector<Ev>& waits) override {
     auto [id, ev] = make_event();
     std::vector<std::shared_ptr<SimEvent>> deps;
@@ -486,7 +492,7 @@ class SimBackend : public Backend {
       const SimTiming& tm = fab_->timing;
       if (tm.verify_bps > 0 || tm.verify_launch_s > 0) {
         int64_t bytes = 0;
-        for (const CheckReq& r : reqs) bytes += r.out ? fp8::packed_len(r.n, r.block) : r.n;
+        for (const CheckReq& r : reqs) bytes += r.out ? packed_len(r) : r.n;
         const double dur = tm.verify_launch_s + (tm.verify_bps > 0 ? double(bytes) / tm.verify_bps : 0.0);
         const double t0 = vclock::now();
         vclock::sleep_until(t0 + dur);
@@ -502,9 +508,11 @@ class SimBackend : public Backend {
           results_[r.slot] = crc32c(r.p, size_t(r.n));
           continue;
         }
-        const int64_t n = r.n / 2;  // fp8 values of the chunk
-        results_[r.slot] = crc32c(r.p, size_t(fp8::packed_len(r.n, r.block)));
-        if (copy)
+        const int64_t n = r.n / 2;  // values of the chunk
+        results_[r.slot] = crc32c(r.p, size_t(packed_len(r)));
+        if (r.format == kPackMxfp4)
+          mxfp4::unpack_host(r.p, r.p + n / 2, n, reinterpret_cast<uint16_t*>(r.out));
+        else
           fp8::unpack_host(r.p, reinterpret_cast<const float*>(r.p + n), n, reinterpret_cast<uint16_t*>(r.out), r.block);
       }
       ev->set(1);

@@ -246,7 +246,7 @@ class HipBackend : public Backend {
     return record(s);
   }
 
-  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block) override {
+  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block, int format) override {
     // bf16 lands in a device scratch chunk, then the gfx950 pack kernel writes
     // the packed chunk into the layer slot. One scratch per copy queue: both
     // steps are ordered on that queue, and packing (~22 us per 64 MiB) is
@@ -265,8 +265,11 @@ class HipBackend : public Backend {
     }
     HIP_OK(hipMemcpyAsync(scratch_[q], src, size_t(n_src), hipMemcpyHostToDevice, s));
     const int64_t n = n_src / 2;
-    HIP_OK(kern::fp8_pack(static_cast<const uint16_t*>(scratch_[q]), n, dst, reinterpret_cast<float*>(dst + n), block,
-                          s));
+    if (format == kPackMxfp4)
+      HIP_OK(kern::mxfp4_pack(static_cast<const uint16_t*>(scratch_[q]), n, dst, dst + n / 2, s));
+    else
+      HIP_OK(kern::fp8_pack(static_cast<const uint16_t*>(scratch_[q]), n, dst, reinterpret_cast<float*>(dst + n), block,
+                            s));
     return record(s);
   }
 
@@ -322,21 +325,24 @@ class HipBackend : public Backend {
     HIP_OK(hipEventRecord(start, verify_));
     std::vector<kern::CrcItem> plain;
     std::vector<kern::FusedItem> fused;
-    int block = 0;
+    int block = 0, format = kPackFp8;
     auto flush_plain = [&] {
       if (!plain.empty()) HIP_OK(kern::crc32c_batch(plain.data(), int(plain.size()), ws_, verify_, verify_cus_));
       plain.clear();
     };
     auto flush_fused = [&] {
-      if (!fused.empty())
+      if (!fused.empty() && format == kPackMxfp4)
+        HIP_OK(kern::mxfp4_verify_unpack_batch(fused.data(), int(fused.size()), ws_, verify_, verify_cus_));
+      else if (!fused.empty())
         HIP_OK(kern::fp8_verify_unpack_batch(fused.data(), int(fused.size()), block, ws_, verify_, verify_cus_));
       fused.clear();
     };
     for (const CheckReq& r : reqs) {
       if (r.n <= 0) continue;
       if (r.out) {
-        if (block && r.block != block) flush_fused();
+        if (block && (r.block != block || r.format != format)) flush_fused();
         block = r.block;
+        format = r.format;
         fused.push_back(kern::FusedItem{r.p, r.n, reinterpret_cast<uint16_t*>(r.out), crc_dev_ + r.slot});
         if (fused.size() == size_t(kern::kCrcBatchMax)) flush_fused();
       } else {

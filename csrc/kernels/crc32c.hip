@@ -1,5 +1,6 @@
 // CRC32C on gfx950 (receiver-side verification of every landed chunk), and
-// the fused CRC32C + fp8 -> bf16 dequantization of packed chunks.
+// the fused CRC32C + fp8 -> bf16 (UnpackVisit) or MXFP4 -> bf16 (Mxfp4Visit)
+// dequantization of packed chunks.
 //
 // CRC is a serial recurrence, so the kernel works with raw (un-inverted) CRC
 // registers, which are linear over GF(2):
@@ -84,6 +85,7 @@
 #include "core/crc32c.h"
 #include "kernels/fp8_cvt.h"
 #include "kernels/kernels.h"
+#include "kernels/mxfp4_cvt.h"
 
 namespace dissem {
 namespace kern {
@@ -676,6 +678,68 @@ struct UnpackVisit {
   }
 };
 
+// Fused verify + unpack of MXFP4-packed chunks (core/mxfp4.h layout
+// [q: n/2 bytes][scales: n/32 E8M0 bytes] per chunk). Every 16-B word of the q
+// region is exactly one scale block: the lane that holds it loads the block's
+// scale byte and converts the block's 64 B of bf16 (element offset 2 * byte
+// offset). The scale bytes are CRC'd like any other bytes and not unpacked.
+//
+// Stores: a lane's 64 B are four 16-B registers. Stored as they are, each store
+// instruction of a wave writes 16 B in every 64 (a quarter of every line it
+// touches): 100 us per 64 MiB source chunk in 16-chunk launches, against 24.5
+// for the fp8 kernel in the same run (profiles/mxfp4). For the words of a full
+// segment whose KiB lies in q, the four lanes m, m + 16, m + 32, m + 48 (words
+// r = 0..3 of one 64-B piece: 256 contiguous output bytes) exchange registers
+// first (row_transpose: register k of lane r <-> register r of lane k), so
+// store instruction k writes 64 contiguous bytes per piece - the granule the
+// fp8 block-32 path writes. The scale prefetch and the LDS-staged, fully
+// coalesced stores of UnpackVisit are not ported.
+struct Mxfp4Visit {
+  int64_t n_q = 0;
+  const uint8_t* scales = nullptr;
+  uint16_t* obase = nullptr;
+  uint8_t* slot = nullptr;  // this wave's LDS slot (set by the kernel; not used for staging here)
+  __device__ void begin(const Seg& sg) {
+    n_q = sg.chunk_len / 17 * 16;  // q bytes of this chunk
+    scales = sg.p - sg.seg_start + n_q;
+    obase = sg.out;
+  }
+  static __device__ __forceinline__ void convert(const u32x4_t& w, uint32_t sb, u32x4_t (&o)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      uint32_t v[4];
+      mxfp4_unpack8(w[k], sb, v);
+      o[k] = u32x4_t{v[0], v[1], v[2], v[3]};
+    }
+  }
+  __device__ void operator()(const u32x4_t& w, int64_t e) {  // e: byte offset in chunk; elements 2e .. 2e + 31
+    if (e >= n_q) return;
+    u32x4_t o[4];
+    convert(w, scales[e >> 4], o);
+    u32x4_t* dst = reinterpret_cast<u32x4_t*>(obase + 2 * e);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(o[k], dst + k);
+  }
+  // word i of a full segment (all lanes active): lane m + 16 r holds bytes
+  // lo = 64 m + 16 r of its KiB
+  __device__ void word(const u32x4_t& w, int64_t e, int) {
+    const int lane = threadIdx.x & 63, r = lane >> 4;
+    const int64_t kib = e - (64 * (lane & 15) + 16 * r);  // wave-uniform
+    if (kib + 1024 > n_q) {  // the KiB holding the q/scale boundary, and the scales
+      (*this)(w, e);
+      return;
+    }
+    u32x4_t o[4];
+    convert(w, scales[e >> 4], o);
+    row_transpose(o[0], o[1], o[2], o[3]);  // register k: bytes 64 k + 16 r of the piece's 256
+    u32x4_t* dst = reinterpret_cast<u32x4_t*>(obase + 2 * (e - 16 * r)) + r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(o[k], dst + 4 * k);
+  }
+  __device__ void prefetch(const Seg&, bool) {}
+  __device__ void advance() {}
+};
+
 // ---- geometry of a launch: which bytes each segment covers, and per item
 // (a chunk whose CRC32C is one result) its segment count, init/xorout term and
 // result word.
@@ -797,8 +861,8 @@ __device__ __forceinline__ void fold_workgroup(const Geo& geo, const uint32_t* v
 // workgroups with 16 table replicas (72 KiB of LDS, + 8 KiB of bf16 staging
 // with an unpack): two workgroups per CU, so one fills its tables and waits
 // for its first loads while the other computes. Workgroups [split_block, ..)
-// take half segments (once_split). BLOCK: the fp8 scale block of the fused
-// unpack (the CRC-only check is crc_walk_kernel below).
+// take half segments (once_split). Visit: the fused unpack (UnpackVisit<fp8
+// scale block> or Mxfp4Visit; the CRC-only check is crc_walk_kernel below).
 // Round 4 measured this shape against the alternatives for the fused path
 // (profiles/r4_nt, r4_kernels_final: 5.3-5.5 TB/s at 512 MiB vs 4.66 for the
 // persistent walk with staged stores, 3.6-4.1 for the walk's other store
@@ -806,12 +870,10 @@ __device__ __forceinline__ void fold_workgroup(const Geo& geo, const uint32_t* v
 // the library. Batching several landed chunks into one launch is what makes
 // it fast at the engine's chunk size: one 64 MiB chunk alone is 264
 // workgroups, less than one per CU slot, and ran at 3.0 TB/s (profiles/r4_sizes).
-template <class Geo, int BLOCK>
+template <class Geo, class Visit>
 __global__ void __launch_bounds__(kWaves16 * 64) __attribute__((amdgpu_waves_per_eu(4)))
 verify_once16_kernel(const Geo geo, int64_t total_segs, int64_t split_block, const uint32_t* __restrict__ sc,
                      uint32_t* __restrict__ acc) {
-  static_assert(BLOCK > 0, "fused only");
-  using Visit = UnpackVisit<BLOCK>;
   // Per wave after the tables: its 1 KiB bf16 staging slot. Bytes 16-31 of a
   // wave's slot carry its fold value and item to thread 0 (its staging is done
   // by then; word 0 may hold a half-pair hand-over). Two 80 KiB workgroups
@@ -1102,7 +1164,7 @@ int once16_per_cu() {
   std::lock_guard<std::mutex> lk(mu);
   if (auto it = by_device.find(dev); it != by_device.end()) return it->second;
   int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, verify_once16_kernel<ChunkGeo, 128>, kWaves16 * 64, 0) !=
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, verify_once16_kernel<ChunkGeo, UnpackVisit<128>>, kWaves16 * 64, 0) !=
       hipSuccess)
     per_cu = 2;
   return by_device[dev] = std::max(1, per_cu);
@@ -1147,7 +1209,7 @@ int64_t min_item_segs(const BatchGeo&) { return 1 << 20; }  // at most kCrcBatch
 
 template <class Geo>
 hipError_t launch(const Geo& geo, int64_t total_segs, int block, const uint32_t* consts, void* ws, hipStream_t s,
-                  int cus) {
+                  int cus, bool mxfp4 = false) {
   if (total_segs <= 0) return hipSuccess;
   if (reinterpret_cast<uintptr_t>(ws) & 7) return hipErrorInvalidValue;  // 64-bit fold words
   auto* acc = static_cast<uint32_t*>(ws);
@@ -1166,12 +1228,16 @@ hipError_t launch(const Geo& geo, int64_t total_segs, int block, const uint32_t*
   }
   const OnceGrid og = once_split(total_segs, cus);
   const dim3 grid(og.blocks), tpb(kWaves16 * 64);
+  if (mxfp4) {
+    verify_once16_kernel<Geo, Mxfp4Visit><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc);
+    return hipGetLastError();
+  }
   switch (block) {
-    case 32: verify_once16_kernel<Geo, 32><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
-    case 64: verify_once16_kernel<Geo, 64><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
-    case 128: verify_once16_kernel<Geo, 128><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
-    case 256: verify_once16_kernel<Geo, 256><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
-    case 512: verify_once16_kernel<Geo, 512><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
+    case 32: verify_once16_kernel<Geo, UnpackVisit<32>><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
+    case 64: verify_once16_kernel<Geo, UnpackVisit<64>><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
+    case 128: verify_once16_kernel<Geo, UnpackVisit<128>><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
+    case 256: verify_once16_kernel<Geo, UnpackVisit<256>><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
+    case 512: verify_once16_kernel<Geo, UnpackVisit<512>><<<grid, tpb, 0, s>>>(geo, total_segs, og.split_block, consts, acc); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -1210,6 +1276,9 @@ hipError_t batch_add(BatchGeo& a, const void* src, int64_t bytes, uint32_t* crc_
 
 // Packed bytes of `src_len` bf16 source bytes (one chunk's worth) with `block` scales.
 int64_t packed_of(int64_t src_len, int block) { return src_len / 2 + src_len / 2 / block * 4; }
+
+// Packed bytes of `src_len` bf16 source bytes as MXFP4 (core/mxfp4.h packed_len).
+int64_t mxfp4_packed_of(int64_t src_len) { return src_len / 4 + src_len / 64; }
 
 bool valid_block(int block) { return block == 32 || block == 64 || block == 128 || block == 256 || block == 512; }
 
@@ -1291,6 +1360,43 @@ hipError_t fp8_verify_unpack_batch(const FusedItem* items, int n, int block, voi
   if (a.n == 0) return hipSuccess;
   for (int j = a.n; j < kCrcBatchMax; ++j) a.seg_base[j + 1] = a.seg_base[a.n];
   return launch(a, a.seg_base[a.n], block, consts, workspace, s, cus);
+}
+
+hipError_t mxfp4_verify_unpack(const void* packed, int64_t src_bytes, int64_t src_chunk, uint16_t* out,
+                               uint32_t* crc_out, void* workspace, hipStream_t s, int cus) {
+  if (src_bytes <= 0) return hipSuccess;
+  if (src_chunk <= 0 || src_chunk % 4096 || src_bytes % 64 || (reinterpret_cast<uintptr_t>(packed) & 15) ||
+      (reinterpret_cast<uintptr_t>(out) & 15))
+    return hipErrorInvalidValue;
+  const int64_t pchunk = mxfp4_packed_of(src_chunk);
+  const int64_t full = src_bytes / src_chunk, tail = src_bytes % src_chunk;
+  const int64_t bytes = full * pchunk + (tail ? mxfp4_packed_of(tail) : 0);
+  const uint32_t* consts = device_consts(s);
+  if (!consts) return hipErrorOutOfMemory;
+  ChunkGeo geo;
+  int64_t total = 0;
+  if (hipError_t e = chunk_geo(packed, bytes, pchunk, crc_out, &geo, &total); e != hipSuccess) return e;
+  geo.out = out;
+  geo.out_chunk_elems = src_chunk / 2;
+  return launch(geo, total, 32, consts, workspace, s, cus, true);
+}
+
+hipError_t mxfp4_verify_unpack_batch(const FusedItem* items, int n, void* workspace, hipStream_t s, int cus) {
+  if (n <= 0) return hipSuccess;
+  if (n > kCrcBatchMax) return hipErrorInvalidValue;
+  const uint32_t* consts = device_consts(s);
+  if (!consts) return hipErrorOutOfMemory;
+  BatchGeo a{};
+  for (int i = 0; i < n; ++i) {
+    const FusedItem& it = items[i];
+    if (it.src_len <= 0) continue;
+    if (it.src_len % 64 || (reinterpret_cast<uintptr_t>(it.out) & 15)) return hipErrorInvalidValue;
+    if (hipError_t e = batch_add(a, it.packed, mxfp4_packed_of(it.src_len), it.crc_out, it.out); e != hipSuccess)
+      return e;
+  }
+  if (a.n == 0) return hipSuccess;
+  for (int j = a.n; j < kCrcBatchMax; ++j) a.seg_base[j + 1] = a.seg_base[a.n];
+  return launch(a, a.seg_base[a.n], 32, consts, workspace, s, cus, true);
 }
 
 }  // namespace kern

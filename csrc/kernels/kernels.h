@@ -84,5 +84,20 @@ struct FusedItem {
 hipError_t fp8_verify_unpack_batch(const FusedItem* items, int n, int block, void* workspace, hipStream_t s,
                                    int cus = 0);
 
+// ---- mxfp4.hip: bf16 -> MXFP4 (e2m1 codes, two per byte, element 2k in the low
+// nibble; one E8M0 scale byte per 32 elements; core/mxfp4.h) and back,
+// bit-exact with the host reference. n a multiple of 32; bf16 16-B, q 4-B aligned.
+hipError_t mxfp4_pack(const uint16_t* bf16, int64_t n, uint8_t* q, uint8_t* scales, hipStream_t s);
+hipError_t mxfp4_unpack(const uint8_t* q, const uint8_t* scales, int64_t n, uint16_t* bf16, hipStream_t s);
+// Whole layer into the chunked packed layout of core/mxfp4.h (one pack launch per chunk).
+hipError_t mxfp4_pack_chunks(const void* src, int64_t src_bytes, int64_t src_chunk, void* dst, hipStream_t s);
+
+// ---- crc32c.hip: the same fused verify + unpack for MXFP4-packed layers and
+// chunks (core/mxfp4.h layout; src_chunk a multiple of 4096, src_bytes and
+// every src_len a multiple of 64).
+hipError_t mxfp4_verify_unpack(const void* packed, int64_t src_bytes, int64_t src_chunk, uint16_t* out,
+                               uint32_t* crc_out, void* workspace, hipStream_t s, int cus = 0);
+hipError_t mxfp4_verify_unpack_batch(const FusedItem* items, int n, void* workspace, hipStream_t s, int cus = 0);
+
 }  // namespace kern
 }  // namespace dissem

@@ -2,15 +2,18 @@
 // AddressSanitizer (`make sanitize`). Exercises the concurrent
 // paths: TCP + in-proc transports, every role/mode on the host engine, and the
 // planned (GPU-schedule) engine on the simulated RCCL fabric with 4 ranks.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
 #include <thread>
+#include <vector>
 
 #include "core/crc32c.h"
 #include "core/vclock.h"
 #include "core/log.h"
+#include "core/mxfp4.h"
 #include "engine/planned_engine.h"
 #include "roles/node.h"
 
@@ -193,10 +196,43 @@ static void planned_sim(int mode, double corrupt = 0, int die = -1, bool crossin
   }
 }
 
+// MXFP4 host codec (core/mxfp4.h) over all 65536 bf16 bit patterns, in natural
+// order and shuffled (NaN, inf and every magnitude mixed within blocks), as a
+// layer with a tail chunk: every unpacked value is NaN (0x7FC0) in a NaN block,
+// else finite with the source's sign, and the unpacked values are fixed points
+// of the codec (pack + unpack gives them back).
+static void mxfp4_roundtrip() {
+  std::vector<uint16_t> x(65536 + 32 * 33);
+  for (size_t i = 0; i < x.size(); ++i) x[i] = uint16_t(i);
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass) std::shuffle(x.begin(), x.end(), std::mt19937(7));
+    const int64_t src = int64_t(x.size()) * 2, chunk = 4096;
+    std::vector<uint8_t> packed(size_t(mxfp4::packed_size(src, chunk))), again(packed.size());
+    std::vector<uint16_t> y(x.size()), z(x.size());
+    EXPECT(mxfp4::source_size(int64_t(packed.size()), chunk) == src);
+    mxfp4::pack_layer_host(reinterpret_cast<const uint8_t*>(x.data()), src, chunk, packed.data());
+    mxfp4::unpack_layer_host(packed.data(), src, chunk, reinterpret_cast<uint8_t*>(y.data()));
+    int bad = 0;
+    for (size_t b = 0; b < x.size() / 32; ++b) {
+      bool nan = false;
+      for (int i = 0; i < 32; ++i) nan = nan || (x[b * 32 + i] & 0x7FFF) > 0x7F80;
+      for (int i = 0; i < 32; ++i) {
+        const uint16_t v = y[b * 32 + i];
+        if (nan) bad += v != 0x7FC0;
+        else bad += (v & 0x7FFF) >= 0x7F80 || ((v ^ x[b * 32 + i]) & 0x8000);  // finite, sign kept
+      }
+    }
+    EXPECT(bad == 0);
+    mxfp4::pack_layer_host(reinterpret_cast<const uint8_t*>(y.data()), src, chunk, again.data());
+    mxfp4::unpack_layer_host(again.data(), src, chunk, reinterpret_cast<uint8_t*>(z.data()));
+    EXPECT(y == z);  // unpacked values are fixed points of the codec
+  }
+}
+
 int main(int argc, char** argv) {
   log::set_level(log::Error);
   // optional: run one case only (0-3 ring modes, 4-6 planned modes 1-3, 7 corruption, 8-9 rank death,
-  // 10 crossing mode-2 chunk jobs, 11-13 planned modes 1-3 on the virtual clock)
+  // 10 crossing mode-2 chunk jobs, 11-13 planned modes 1-3 on the virtual clock, 14 the MXFP4 host codec)
   const int only = argc > 1 ? atoi(argv[1]) : -1;
   auto on = [&](int k) { return only < 0 || only == k; };
   for (int mode = 0; mode <= 3; ++mode) {
@@ -212,6 +248,7 @@ int main(int argc, char** argv) {
   if (on(10)) planned_sim(2, 0, -1, true);
   for (int mode = 1; mode <= 3; ++mode)
     if (on(10 + mode)) planned_sim(mode, 0, -1, mode == 2, true);
+  if (on(14)) mxfp4_roundtrip();
   if (failures) {
     fprintf(stderr, "%d failures\n", failures);
     return 1;

@@ -2,10 +2,17 @@
 // Prints, for a few fp8 codes and scales, the bf16 results of
 // v_cvt_scalef32_pk_bf16_fp8 next to code * scale, and the fp8 codes that
 // v_cvt_scalef32_pk_fp8_bf16 produces for bf16 inputs.
+//
+// MXFP4 (core/mxfp4.h): exhaustive comparison of v_cvt_scalef32_pk_fp4_bf16 and
+// v_cvt_scalef32_pk_bf16_fp4 with the integer reference of kernels/mxfp4_cvt.h
+// - every bf16 pattern against every scale 2^E, E in [-126, 125], and every
+// code byte against every scale byte - as mismatch counts per class of input.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstring>
+
+#include "kernels/mxfp4_cvt.h"
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
@@ -23,6 +30,119 @@ __global__ void pack_probe(const uint32_t* bf16pairs, const float* scales, int n
   i16x2 old = {0, 0};
   auto r = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(old, __builtin_bit_cast(bf16x2, bf16pairs[i]), scales[i], false);
   out[i] = uint32_t(__builtin_bit_cast(uint32_t, r));
+}
+
+// |x| (bf16 bits `a`, finite, at most 6 * 2^e) -> the e2m1 magnitude code of
+// a * 2^-e, nearest with ties to the even code, in integer arithmetic: 4y =
+// sig >> rs with a sticky bit, against the midpoints 0.25 ... 5 (all multiples
+// of 0.25). The reference of the pack probe.
+__device__ static uint32_t quant_bits(uint32_t a, int e) {
+  const uint32_t ea = a >> 7;
+  const uint32_t sig = ea ? 0x80u | (a & 0x7Fu) : a & 0x7Fu;
+  const int rs0 = e + 132 - int(ea ? ea : 1u);  // >= 3 for |x| <= 6 * 2^e
+  const uint32_t rs = uint32_t(rs0 > 31 ? 31 : rs0 < 0 ? 0 : rs0);
+  const uint32_t key = ((sig >> rs) << 1) | ((sig & ((1u << rs) - 1u)) ? 1u : 0u);  // 2 * floor(4y), odd: a remainder
+  return (key > 2u) + (key >= 6u) + (key > 10u) + (key >= 14u) + (key > 20u) + (key >= 28u) + (key > 40u);
+}
+
+// One code (low 4 bits) times 2^(sb - 127) as bf16 bits, in integer arithmetic.
+__device__ static uint32_t bf16_bits(uint32_t code, uint32_t sb) {
+  if (sb == 0xFFu) return 0x7FC0u;
+  const uint32_t m = code & 7u, sign = (code & 8u) << 12;
+  if (m == 0) return sign;
+  // value = (1 + mant / 128) * 2^eo: 0.5, 1, 1.5, 2, 3, 4, 6
+  const int eo = int(m >> 1) - 1;
+  const uint32_t mant = (m & 1u) && m > 1 ? 0x40u : 0u;
+  const int ee = int(sb) + eo;  // biased bf16 exponent
+  if (ee >= 255) return sign | 0x7F80u;
+  if (ee >= 1) return sign | (uint32_t(ee) << 7) | mant;
+  return sign | ((0x80u | mant) >> (1 - ee));  // subnormal: exact, at most 2 bits shifted out of 0x80 / 1 of 0xC0
+}
+
+// ---- MXFP4. Classes of pack inputs (x, E), counted as [total, mismatches]:
+enum { kInRange, kInRangeSub, kTie, kZero, kAbove, kInf, kNan, kPackClasses };
+static const char* kPackClass[] = {"in_range_normal", "in_range_bf16_subnormal", "code_boundary", "zero",
+                                   "above_6x2^E_finite", "inf", "nan"};
+
+// blockIdx.y = E + 126; thread = bf16 pattern (the other half of the pair is its negation)
+__global__ void fp4_pack_probe(unsigned long long* cnt, uint32_t* first_bad) {
+  const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int e = int(blockIdx.y) - 126;
+  const uint32_t a = x & 0x7FFFu, lim = (uint32_t(e + 129) << 7) | 0x40u;
+  const float s = __uint_as_float(uint32_t(e + 127) << 23);
+  const uint32_t pair = x | ((x ^ 0x8000u) << 16);
+  const uint32_t r = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(0u, __builtin_bit_cast(bf16x2, pair), s, 0);
+  int cls;
+  uint32_t want;
+  if (a > 0x7F80u) {
+    cls = kNan, want = 7;  // no reference: counted as "mismatch" unless it saturates
+  } else if (a == 0x7F80u) {
+    cls = kInf, want = 7;
+  } else if (a > lim) {
+    cls = kAbove, want = 7;
+  } else {
+    want = quant_bits(a, e);
+    // code_boundary: a bf16 neighbour of x rounds to another code (the ties are among these)
+    const uint32_t up = quant_bits(a + 1 <= lim ? a + 1 : a, e);
+    const uint32_t dn = quant_bits(a ? a - 1 : 0, e);
+    cls = a == 0 ? kZero : (a < 0x80u ? kInRangeSub : ((up != want) != (dn != want) && up != dn ? kTie : kInRange));
+  }
+  const uint32_t lo = want | ((x >> 12) & 8u), hi = want | (((x ^ 0x8000u) >> 12) & 8u);
+  const bool bad = (r & 0xFFu) != (lo | (hi << 4)) || (r >> 8) != 0;
+  atomicAdd(&cnt[2 * cls], 1ull);
+  if (bad) {
+    if (atomicAdd(&cnt[2 * cls + 1], 1ull) == 0) {
+      first_bad[3 * cls] = x;
+      first_bad[3 * cls + 1] = uint32_t(e);
+      first_bad[3 * cls + 2] = r;
+    }
+  }
+}
+
+// blockIdx.x = scale byte, thread = code byte (replicated in the 4 bytes, each SEL tried)
+__global__ void fp4_unpack_probe(unsigned long long* bad_by_scale, uint32_t* first_bad) {
+  const uint32_t sb = blockIdx.x, b = threadIdx.x;
+  const float s = __uint_as_float(sb << 23);
+  const uint32_t w = b * 0x01010101u;
+  const uint32_t want = bf16_bits(b, sb) | (bf16_bits(b >> 4, sb) << 16);
+  const uint32_t got[4] = {dissem::kern::fp4x2_to_bf16x2<0>(w, s), dissem::kern::fp4x2_to_bf16x2<1>(w, s),
+                           dissem::kern::fp4x2_to_bf16x2<2>(w, s), dissem::kern::fp4x2_to_bf16x2<3>(w, s)};
+  for (int k = 0; k < 4; ++k)
+    if (got[k] != want && atomicAdd(&bad_by_scale[sb], 1ull) == 0) {
+      first_bad[2 * sb] = b;
+      first_bad[2 * sb + 1] = got[k];
+    }
+}
+
+static void mxfp4_probe() {
+  unsigned long long *cnt, *ubad;
+  uint32_t *pfirst, *ufirst;
+  hipMalloc(&cnt, 2 * kPackClasses * 8);
+  hipMalloc(&pfirst, 3 * kPackClasses * 4);
+  hipMalloc(&ubad, 256 * 8);
+  hipMalloc(&ufirst, 512 * 4);
+  hipMemset(cnt, 0, 2 * kPackClasses * 8);
+  hipMemset(pfirst, 0, 3 * kPackClasses * 4);
+  hipMemset(ubad, 0, 256 * 8);
+  hipMemset(ufirst, 0, 512 * 4);
+  fp4_pack_probe<<<dim3(256, 252), 256>>>(cnt, pfirst);
+  fp4_unpack_probe<<<256, 256>>>(ubad, ufirst);
+  unsigned long long hc[2 * kPackClasses], hu[256];
+  uint32_t hp[3 * kPackClasses], hf[512];
+  hipMemcpy(hc, cnt, sizeof hc, hipMemcpyDeviceToHost);
+  hipMemcpy(hp, pfirst, sizeof hp, hipMemcpyDeviceToHost);
+  hipMemcpy(hu, ubad, sizeof hu, hipMemcpyDeviceToHost);
+  hipMemcpy(hf, ufirst, sizeof hf, hipMemcpyDeviceToHost);
+  for (int c = 0; c < kPackClasses; ++c)
+    printf("{\"op\": \"fp4_pack\", \"class\": \"%s\", \"inputs\": %llu, \"mismatches\": %llu, "
+           "\"first\": {\"bf16\": \"0x%04x\", \"E\": %d, \"got\": \"0x%08x\"}}\n",
+           kPackClass[c], hc[2 * c], hc[2 * c + 1], hp[3 * c], int(hp[3 * c + 1]), hp[3 * c + 2]);
+  unsigned long long mid = 0;
+  for (int sb = 2; sb <= 252; ++sb) mid += hu[sb];
+  printf("{\"op\": \"fp4_unpack\", \"scale_bytes\": \"2..252\", \"mismatches\": %llu}\n", mid);
+  for (int sb : {0, 1, 253, 254, 255})
+    printf("{\"op\": \"fp4_unpack\", \"scale_bytes\": \"%d\", \"mismatches\": %llu, \"first\": "
+           "{\"codes\": \"0x%02x\", \"got\": \"0x%08x\"}}\n", sb, hu[sb], hf[2 * sb], hf[2 * sb + 1]);
 }
 
 static float bf16f(uint16_t b) {
@@ -70,5 +190,6 @@ int main() {
   for (int i = 0; i < n; ++i)
     printf("{\"op\": \"pack\", \"in\": [%g, %g], \"scale\": %g, \"codes\": \"0x%04x\"}\n", vals[i][0], vals[i][1],
            pscales[i], out[i] & 0xFFFF);
-  return 0;
+  mxfp4_probe();
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
 }

@@ -64,10 +64,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="data plane: host (TCP into RAM, the reference) or rccl (RCCL/xGMI into HBM); "
                         "auto = rccl under torchrun with a GPU visible, else host")
     p.add_argument("--chunk-mib", type=int, default=64)
-    p.add_argument("--pack", default="none", choices=["none", "fp8"],
-                   help="fp8: bf16 layers are packed to block-scaled e4m3fn on staging (wire + HBM format)")
+    p.add_argument("--pack", default="none", choices=["none", "fp8", "mxfp4"],
+                   help="fp8: bf16 layers are packed to block-scaled e4m3fn on staging (wire + HBM format); "
+                        "mxfp4: to OCP MXFP4 (e2m1 codes, one E8M0 scale per 32 values; 17/64 of the bf16 bytes)")
     p.add_argument("--store", default="packed", choices=["packed", "bf16"],
-                   help="with --pack fp8: bf16 = also keep each layer dequantized to bf16 in HBM (fused "
+                   help="with --pack fp8 or mxfp4: bf16 = also keep each layer dequantized to bf16 in HBM (fused "
                         "verify+unpack kernel on every landed chunk)")
     p.add_argument("--verify", default="crc32c", choices=["none", "crc32c"])
     p.add_argument("--weights", default="", metavar="PRESET",

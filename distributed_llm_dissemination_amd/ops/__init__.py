@@ -10,6 +10,12 @@ from .kernels import (  # noqa: F401
     fp8_unpack,
     fp8_verify_unpack,
     fp8_verify_unpack_chunks,
+    mxfp4_pack,
+    mxfp4_pack_layer,
+    mxfp4_packed_size,
+    mxfp4_unpack,
+    mxfp4_verify_unpack,
+    mxfp4_verify_unpack_chunks,
 )
 
 __all__ = [
@@ -22,4 +28,10 @@ __all__ = [
     "fp8_unpack",
     "fp8_verify_unpack",
     "fp8_verify_unpack_chunks",
+    "mxfp4_pack",
+    "mxfp4_pack_layer",
+    "mxfp4_packed_size",
+    "mxfp4_unpack",
+    "mxfp4_verify_unpack",
+    "mxfp4_verify_unpack_chunks",
 ]

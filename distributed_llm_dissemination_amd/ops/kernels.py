@@ -10,6 +10,7 @@ must never be handed a buffer smaller than its grid assumes).
     x = torch.randn(1 << 24, dtype=torch.bfloat16, device="cuda")
     q, s = ops.fp8_pack(x)                    # OCP e4m3fn + one f32 scale per 128 values
     y = ops.fp8_unpack(q, s)                  # bf16 again
+    q4, s4 = ops.mxfp4_pack(x)                # MXFP4: e2m1 pairs + one E8M0 scale per 32 values
     crc = ops.crc32c(x.view(torch.uint8), 64 << 20)   # CRC32C per 64 MiB chunk
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
@@ -35,6 +36,12 @@ __all__ = [
     "fp8_verify_unpack",
     "fp8_verify_unpack_chunks",
     "fp8_packed_size",
+    "mxfp4_pack",
+    "mxfp4_unpack",
+    "mxfp4_pack_layer",
+    "mxfp4_verify_unpack",
+    "mxfp4_verify_unpack_chunks",
+    "mxfp4_packed_size",
 ]
 
 _FP8_BLOCKS = (32, 64, 128, 256, 512)
@@ -188,4 +195,115 @@ def fp8_verify_unpack_chunks(chunks: List[Tuple[torch.Tensor, int]], block: int 
     crcs = torch.empty(len(chunks), dtype=torch.int32, device=dev)
     ws = torch.zeros(_core.crc32c_batch_workspace_bytes(), dtype=torch.uint8, device=dev)
     _core.fp8_verify_unpack_batch_async(items, block, crcs.data_ptr(), ws.data_ptr(), _stream())
+    return outs, crcs
+
+
+# ---- MXFP4 (core/mxfp4.h): e2m1 codes, two per byte, one E8M0 scale byte per 32 values
+
+_MX_BLOCK = 32
+
+
+def mxfp4_pack(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bf16 -> MXFP4 (OCP MX): e2m1 codes, two per byte (element 2k in the low
+    nibble), and one E8M0 scale byte per 32 values (2^E, the smallest E in
+    [-126, 125] with the block's finite amax <= 6 * 2^E; core/mxfp4.h). Values
+    round to the nearest code, ties to the even one; +-inf saturate to +-6 * 2^E;
+    a block that holds a NaN is stored as scale 0xFF with zero codes.
+    Returns (q: uint8 [n / 2], scales: uint8 [n / 32]);
+    ``q.view(torch.float4_e2m1fn_x2)`` and ``scales.view(torch.float8_e8m0fnu)``
+    are the matching torch dtypes."""
+    _check_dev(x, "x", torch.bfloat16)
+    n = x.numel()
+    if n % _MX_BLOCK:
+        raise ValueError(f"numel ({n}) must be a multiple of {_MX_BLOCK}")
+    q = torch.empty(n // 2, dtype=torch.uint8, device=x.device)
+    s = torch.empty(n // _MX_BLOCK, dtype=torch.uint8, device=x.device)
+    _core.mxfp4_pack(x.data_ptr(), n, q.data_ptr(), s.data_ptr(), _stream())
+    return q, s
+
+
+def _as_bytes(t: torch.Tensor, name: str, other) -> torch.Tensor:
+    if t.dtype == torch.uint8:
+        return t
+    if other is not None and t.dtype == other:
+        return t.view(torch.uint8)
+    raise ValueError(f"{name} must be uint8" + (f" or {other}" if other is not None else ""))
+
+
+def mxfp4_unpack(q: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Inverse of `mxfp4_pack`: bf16 values code * 2^(scale - 127), exact (bf16
+    subnormals included); scale 0xFF gives NaN (0x7FC0) for the whole block.
+    `q` uint8 [n / 2] (or its ``torch.float4_e2m1fn_x2`` view), `scales` uint8
+    [n / 32] (or its ``torch.float8_e8m0fnu`` view)."""
+    q = _as_bytes(q, "q", getattr(torch, "float4_e2m1fn_x2", None))
+    scales = _as_bytes(scales, "scales", getattr(torch, "float8_e8m0fnu", None))
+    _check_dev(q, "q")
+    _check_dev(scales, "scales", align=1)
+    n = q.numel() * 2
+    if n % _MX_BLOCK or scales.numel() != n // _MX_BLOCK:
+        raise ValueError("scales must hold one byte per 16 bytes of q")
+    y = torch.empty(n, dtype=torch.bfloat16, device=q.device)
+    _core.mxfp4_unpack(q.data_ptr(), scales.data_ptr(), n, y.data_ptr(), _stream())
+    return y
+
+
+def mxfp4_packed_size(src_bytes: int, chunk_bytes: int) -> int:
+    """Bytes of a bf16 layer of `src_bytes` in the chunked MXFP4 wire/HBM layout."""
+    return _core.mxfp4_packed_size(src_bytes, chunk_bytes)
+
+
+def mxfp4_pack_layer(x: torch.Tensor, chunk_bytes: int) -> torch.Tensor:
+    """A whole bf16 layer into the data engine's packed layout (core/mxfp4.h): per
+    source chunk of `chunk_bytes`, [e2m1 codes][E8M0 scales]. Returns uint8."""
+    _check_dev(x, "x", torch.bfloat16)
+    src = _nbytes(x)
+    if chunk_bytes <= 0 or chunk_bytes % 4096 or src % (2 * _MX_BLOCK):
+        raise ValueError("chunk_bytes must be a positive multiple of 4096 and the layer a multiple of 64 B")
+    out = torch.empty(mxfp4_packed_size(src, chunk_bytes), dtype=torch.uint8, device=x.device)
+    _core.mxfp4_pack_chunks(x.data_ptr(), src, chunk_bytes, out.data_ptr(), _stream())
+    return out
+
+
+def mxfp4_verify_unpack(packed: torch.Tensor, src_bytes: int, chunk_bytes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One fused pass over an MXFP4-packed layer: CRC32C of every packed chunk and
+    the dequantized bf16 layer. Returns (bf16 [src_bytes / 2], crcs int32 [chunks])."""
+    _check_dev(packed, "packed", torch.uint8)
+    if chunk_bytes <= 0 or chunk_bytes % 4096 or src_bytes <= 0 or src_bytes % (2 * _MX_BLOCK):
+        raise ValueError("bad chunk_bytes / src_bytes")
+    pbytes = mxfp4_packed_size(src_bytes, chunk_bytes)
+    if packed.numel() < pbytes:
+        raise ValueError(f"packed holds {packed.numel()} bytes, the layout needs {pbytes}")
+    pchunk = chunk_bytes // 4 + chunk_bytes // 64
+    nchunks = (pbytes + pchunk - 1) // pchunk
+    out = torch.empty(src_bytes // 2, dtype=torch.bfloat16, device=packed.device)
+    crcs = torch.empty(nchunks, dtype=torch.int32, device=packed.device)
+    ws = torch.zeros(_core.crc32c_workspace_bytes(pbytes, pchunk), dtype=torch.uint8, device=packed.device)
+    _core.mxfp4_verify_unpack_async(packed.data_ptr(), src_bytes, chunk_bytes, out.data_ptr(), crcs.data_ptr(),
+                                    ws.data_ptr(), _stream())
+    return out, crcs
+
+
+def mxfp4_verify_unpack_chunks(chunks: List[Tuple[torch.Tensor, int]]) -> Tuple[List[torch.Tensor], torch.Tensor]:
+    """The engine's batched form: independent packed chunks [(packed uint8, src_len), ...]
+    (each the core/mxfp4.h image of `src_len` bf16 bytes, up to `_core.crc32c_batch_max()`
+    of them) checked and dequantized in ONE launch. Returns ([bf16 per chunk], crcs int32)."""
+    if not chunks or len(chunks) > _core.crc32c_batch_max():
+        raise ValueError(f"1 to {_core.crc32c_batch_max()} chunks per launch")
+    outs, items = [], []
+    dev = chunks[0][0].device
+    for packed, src_len in chunks:
+        _check_dev(packed, "packed", torch.uint8)
+        if packed.device != dev:
+            raise ValueError("every chunk of one launch must be on the same GPU")
+        if src_len <= 0 or src_len % (2 * _MX_BLOCK):
+            raise ValueError("src_len must be a positive multiple of 64")
+        need = src_len // 4 + src_len // 64
+        if packed.numel() < need:
+            raise ValueError(f"packed chunk holds {packed.numel()} bytes, its layout needs {need}")
+        y = torch.empty(src_len // 2, dtype=torch.bfloat16, device=dev)
+        outs.append(y)
+        items.append((packed.data_ptr(), src_len, y.data_ptr()))
+    crcs = torch.empty(len(chunks), dtype=torch.int32, device=dev)
+    ws = torch.zeros(_core.crc32c_batch_workspace_bytes(), dtype=torch.uint8, device=dev)
+    _core.mxfp4_verify_unpack_batch_async(items, crcs.data_ptr(), ws.data_ptr(), _stream())
     return outs, crcs

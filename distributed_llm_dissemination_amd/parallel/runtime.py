@@ -167,14 +167,19 @@ class Runtime:
         self.engine_kind = engine
         self.storage_path = storage_path
         self.chunk_bytes = cfg.chunk_bytes or chunk_bytes
-        if pack not in ("none", "fp8"):
+        if pack not in ("none", "fp8", "mxfp4"):
             raise ValueError(f"unknown pack format {pack!r}")
+        if pack == "mxfp4":
+            # OCP MX fixes the scale block at 32 elements (core/mxfp4.h)
+            if pack_block not in (32, 128):  # 128: the argument's default
+                raise ValueError(f"--pack mxfp4 has a fixed scale block of 32 elements, not {pack_block}")
+            pack_block = 32
         if pack != "none" and engine not in ("rccl", "sim"):
             raise ValueError("--pack needs the planned (rccl/sim) data engine")
         if store not in ("packed", "bf16"):
             raise ValueError(f"unknown store format {store!r}")
-        if store == "bf16" and pack != "fp8":
-            raise ValueError("--store bf16 dequantizes fp8-packed layers: it needs --pack fp8")
+        if store == "bf16" and pack == "none":
+            raise ValueError("--store bf16 dequantizes packed layers: it needs --pack fp8 or --pack mxfp4")
         self.pack = pack
         self.store = store
         self.pack_block = pack_block
@@ -226,6 +231,11 @@ class Runtime:
             if bad or self.chunk_bytes % unit:
                 raise ValueError(f"--pack fp8 needs layer sizes and the chunk size to be multiples of {unit} B "
                                  f"(2 bytes x {pack_block}-element scale blocks); layers {sorted(bad)[:8]} are not")
+        elif pack == "mxfp4":
+            bad = {l: s for l, s in self.sizes.items() if s % 64}
+            if bad or self.chunk_bytes % 1024:
+                raise ValueError("--pack mxfp4 needs layer sizes that are multiples of 64 B (32 bf16 values per "
+                                 f"scale) and a chunk size that is a multiple of 1024 B; layers {sorted(bad)[:8]} are not")
         self.epoch = 0
         self._closed = False
         self.device: Optional[int] = None
@@ -263,7 +273,7 @@ class Runtime:
             pcfg.chunk_bytes = self.chunk_bytes
             pcfg.verify = verify
             pcfg.poison = poison
-            pcfg.pack = 1 if pack == "fp8" else 0
+            pcfg.pack = {"none": 0, "fp8": 1, "mxfp4": 2}[pack]
             pcfg.pack_block = pack_block
             pcfg.unpack_store = store == "bf16"
             pcfg.inject_corrupt = inject_corrupt
@@ -295,7 +305,7 @@ class Runtime:
             self.engine = None  # host engines are per session (they bind to one node)
         else:
             raise ValueError(f"unknown engine {engine}")
-        # Bytes of each layer in the target tier and on the wire (packed with --pack fp8),
+        # Bytes of each layer in the target tier and on the wire (packed with --pack fp8 / mxfp4),
         # and the chunk grid transfers/CRCs run on.
         if self.engine is not None:
             self.slot_sizes = {l: self.engine.slot_size(s) for l, s in self.sizes.items()}
@@ -351,16 +361,19 @@ class Runtime:
     def _gen_layer(self, layer: int, size: int, seed: int, host_buf=None) -> None:
         """Generate a layer's source bytes (layer_source, or random bf16 bit
         patterns), optionally copy them to `host_buf`, put the target-tier image
-        (packed with --pack fp8) into the layer's HBM slot and record its CRC
+        (packed with --pack fp8 / mxfp4) into the layer's HBM slot and record its CRC
         manifest."""
         slot = self.engine.device_ptr(layer)
         ssz = self.slot_sizes[layer]
         if self.engine_kind == "rccl":
-            if self.pack == "fp8":
+            if self.pack != "none":
                 tmp = _core.device_malloc(size)
                 try:
                     self._fill_from_source(tmp, layer, size, seed, host_buf)
-                    _core.fp8_pack_chunks(tmp, size, self.chunk_bytes, self.pack_block, slot)
+                    if self.pack == "mxfp4":
+                        _core.mxfp4_pack_chunks(tmp, size, self.chunk_bytes, slot)
+                    else:
+                        _core.fp8_pack_chunks(tmp, size, self.chunk_bytes, self.pack_block, slot)
                     _core.device_synchronize()
                 finally:
                     _core.device_free(tmp)
@@ -372,6 +385,8 @@ class Runtime:
                 _core.sim_write(host_buf.ptr, data)
             if self.pack == "fp8":
                 data = _core.fp8_pack_layer_host(data, self.chunk_bytes, self.pack_block)
+            elif self.pack == "mxfp4":
+                data = _core.mxfp4_pack_layer_host(data, self.chunk_bytes)
             _core.sim_write(slot, data)
         self.engine.set_manifest(layer, _core.CrcManifest(self.grid, self._dev_crc(slot, ssz)))
 
@@ -543,7 +558,7 @@ class Runtime:
             raise ValueError(
                 f"node {self.node_id}: its {len(layers)} layer slots need {need / 2**30:.1f} GiB of HBM but only "
                 f"{free / 2**30:.1f} of {total / 2**30:.1f} GiB are free (keeping {self.HBM_HEADROOM >> 30} GiB "
-                f"headroom); use --pack fp8 or an assignment that partitions the layers")
+                f"headroom); use --pack fp8 or --pack mxfp4, or an assignment that partitions the layers")
 
     # ------------------------------------------------------ persist / resume
     PERSIST_MANIFEST = "manifest.json"
@@ -1103,7 +1118,7 @@ class Runtime:
                 "lane_busy_ms": list(es.lane_busy_ms)}
 
     def layer_bytes(self, layer: int) -> bytes:
-        """Bytes of a layer in this rank's target tier (packed with --pack fp8)."""
+        """Bytes of a layer in this rank's target tier (packed with --pack fp8 / mxfp4)."""
         if self.engine is not None:
             ptr = self.engine.device_ptr(layer)
             n = self.slot_sizes[layer]
@@ -1118,7 +1133,7 @@ class Runtime:
     def unpacked_layer_bytes(self, layer: int) -> bytes:
         """A packed layer dequantized back to bf16 after checking every packed chunk
         against the manifest (rccl: the fused verify+unpack kernel, one pass over HBM)."""
-        if self.pack != "fp8":
+        if self.pack == "none":
             return self.layer_bytes(layer)
         size = self.sizes[layer]
         if self.store == "bf16":
@@ -1135,11 +1150,17 @@ class Runtime:
         if self.engine_kind == "sim":
             packed = _core.sim_read(ptr, self.slot_sizes[layer])
             got = _core.host_crc32c_chunks(ptr, self.slot_sizes[layer], self.grid)
-            out = _core.fp8_unpack_layer_host(packed, size, self.chunk_bytes, self.pack_block)
+            if self.pack == "mxfp4":
+                out = _core.mxfp4_unpack_layer_host(packed, size, self.chunk_bytes)
+            else:
+                out = _core.fp8_unpack_layer_host(packed, size, self.chunk_bytes, self.pack_block)
         else:
             dev = _core.device_malloc(size)
             try:
-                got = _core.fp8_verify_unpack(ptr, size, self.chunk_bytes, self.pack_block, dev)
+                if self.pack == "mxfp4":
+                    got = _core.mxfp4_verify_unpack(ptr, size, self.chunk_bytes, dev)
+                else:
+                    got = _core.fp8_verify_unpack(ptr, size, self.chunk_bytes, self.pack_block, dev)
                 buf = _core.HostBuffer.malloc(size)
                 _core.memcpy(buf.ptr, dev, size)
                 out = buf.bytes()
@@ -1155,14 +1176,14 @@ class Runtime:
         """The layer as this rank holds it in HBM, as a uint8 torch tensor.
 
         rccl engine: a zero-copy view of the layer's HBM slot (the packed image
-        with --pack fp8; ``unpacked=True`` with --store bf16: the dequantized bf16
+        with --pack fp8 / mxfp4; ``unpacked=True`` with --store bf16: the dequantized bf16
         image the fused verify+unpack wrote), valid until close(). The view keeps
         this Runtime alive. Other engines: a CPU copy of the same bytes."""
         import torch
 
         if self.engine is None:
             return torch.frombuffer(bytearray(self.layer_bytes(layer)), dtype=torch.uint8)
-        if unpacked and self.pack == "fp8":
+        if unpacked and self.pack != "none":
             if self.store != "bf16":
                 raise ValueError("unpacked views need --store bf16 (use unpacked_layer_bytes for a copy)")
             ptr, n = self.engine.unpacked_ptr(layer), self.sizes[layer]
@@ -1180,10 +1201,10 @@ class Runtime:
     def layer_params(self, layer: int, spec):
         """Named bf16 parameter views of a layer that holds a models/weights.py
         blob: zero-copy in HBM on the rccl engine (the dequantized image with
-        --pack fp8 --store bf16), CPU copies otherwise."""
+        --pack fp8 / mxfp4 and --store bf16), CPU copies otherwise."""
         from ..models.weights import unflatten
 
-        if self.pack == "fp8" and self.store != "bf16":
+        if self.pack != "none" and self.store != "bf16":
             import torch
 
             return unflatten(torch.frombuffer(bytearray(self.unpacked_layer_bytes(layer)), dtype=torch.uint8), spec)
