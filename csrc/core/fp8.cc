@@ -76,7 +76,9 @@ void pack_host(const uint16_t* in, int64_t n, uint8_t* q, float* scales, int blo
 }
 
 void unpack_host(const uint8_t* q, const float* scales, int64_t n, uint16_t* out, int block) {
-  for (int64_t i = 0; i < n; ++i) out[i] = f32_to_bf16(e4m3_to_f32(q[i]) * scales[i / block]);
+  // a NaN code of either sign: 0xFFC0, the NaN v_cvt_scalef32_pk_bf16_fp8 gives for both (core/fp8.h)
+  for (int64_t i = 0; i < n; ++i)
+    out[i] = (q[i] & 0x7F) == 0x7F ? uint16_t(0xFFC0) : f32_to_bf16(e4m3_to_f32(q[i]) * scales[i / block]);
 }
 
 void pack_layer_host(const uint8_t* src, int64_t src_bytes, int64_t src_chunk, int block, uint8_t* dst) {

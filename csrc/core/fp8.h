@@ -10,9 +10,29 @@
 // finite values (E = 0 if none, E >= -126): an E8M0-valued scale (stored as
 // f32), so gfx950's scaled conversions (v_cvt_scalef32_pk_bf16_fp8, which
 // apply only the scale's exponent) dequantize a pair of values in one
-// instruction, and q * 2^E is exact in bf16 (sat_limit keeps it finite). Packed chunks are laid end to end, so the
-// packed layer has its own uniform chunk grid of packed_chunk(src_chunk) bytes
-// and every transfer, CRC and retry runs on that grid unchanged.
+// instruction. Packed chunks are laid end to end, so the packed layer has its
+// own uniform chunk grid of packed_chunk(src_chunk) bytes and every transfer,
+// CRC and retry runs on that grid unchanged.
+//
+// Unpack gives q * 2^E rounded to bf16, to nearest and ties to even. The
+// product is exact (a 4-bit significand) wherever it is a multiple of bf16's
+// smallest subnormal, 2^-133: for every code at E >= -124. It is rounded for
+// 48 (code, E) pairs: at E = -126 the codes +-{1, 2, 3, 5, 6, 7, 9, 10, 11, 13,
+// 14, 15, 17, 19, 21, 23} and at E = -125 the codes +-{1, 3, 5, 7, 9, 11, 13, 15}
+// (2^-135 and 2^-134 steps; pack writes such codes for blocks of bf16
+// subnormals). From E = -118 down many exact products are bf16 subnormals. The
+// host codec (an f32 product, then round-to-nearest-even to bf16),
+// v_cvt_scalef32_pk_bf16_fp8 in both kernels (measured on MI355X for every
+// code at every E) and the tests' numpy reference agree on all of them bit for
+// bit. sat_limit keeps every product pack can write finite; the codes
+// +-0x78..0x7E at E = 120 (256 * 2^120 and more), which pack never writes,
+// are outside the format and their value is unspecified (host and kernels
+// happen to agree on +-inf).
+//
+// NaN packs to 0x7F | the input's sign. A NaN code of either sign unpacks to
+// the bf16 NaN 0xFFC0: that is what v_cvt_scalef32_pk_bf16_fp8 gives for both,
+// and the host codec writes the same bits. -0 and negative values that round
+// to zero keep their sign (0x80).
 #pragma once
 
 #include <cstdint>
@@ -62,8 +82,12 @@ inline int scale_exp(uint32_t amax_bits) {
 // 256 * 2^120 would overflow bf16 on unpack (the bf16 maximum is 255 * 2^120).
 inline float sat_limit(int e) { return e >= 120 ? 240.0f : 448.0f; }
 
-// Host reference (bit-exact with the gfx950 kernel except where the hardware
-// converter double-rounds values within 2^-18 of a rounding tie).
+// Host reference, byte for byte the gfx950 pack kernel on every bf16 input:
+// x * 2^-E has at most 8 significant bits, so it is either exactly on a
+// rounding tie (1/16 of all values) or more than 2^-8 of its own magnitude
+// away from one, and host and hardware round both cases alike. Only for general f32
+// input (not reachable through pack) does v_cvt_pk_fp8_f32 double-round values
+// within 2^-18 of a tie (168.0000153 -> 160, not 176), where f32_to_e4m3 does not.
 uint8_t f32_to_e4m3(float x);  // RNE, finite |x| <= 448 expected, NaN -> 0x7F|sign
 float e4m3_to_f32(uint8_t q);
 void pack_host(const uint16_t* bf16, int64_t n, uint8_t* q, float* scales, int block);

@@ -5,11 +5,11 @@
 // per `block` elements (core/fp8.h: the smallest E with amax <= 448 * 2^E over
 // the block's finite values), stored as f32. Pack scales by the exact 2^-E and
 // converts with v_cvt_pk_fp8_f32 (+-inf saturate to +-448 - 240 in the top
-// binade, core/fp8.h sat_limit - and NaN stays NaN
-// 0x7F - random bf16 payload bit patterns contain both); unpack is
+// binade, core/fp8.h sat_limit - and NaN stays NaN, 0x7F with the input's
+// sign - random bf16 payload bit patterns contain both); unpack is
 // v_cvt_scalef32_pk_bf16_fp8: fp8 pair -> scaled bf16 pair in one instruction
-// (the scale's exponent is applied, exact for a power of two), where the f32
-// path took 4 VALU per pair (convert, 2 multiplies, pack to bf16).
+// (the scale's exponent is applied and the product rounded to bf16, core/fp8.h),
+// where the f32 path took 4 VALU per pair (convert, 2 multiplies, pack to bf16).
 //
 // Each thread moves 8 elements: a 16-B bf16 load and an 8-B fp8 store (pack),
 // or the reverse (unpack). A block of `block` elements is handled by
@@ -40,6 +40,17 @@ __device__ inline int scale_exp(uint32_t amax_bits) {
 
 __device__ inline bool finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
 
+// q: the codes of the four bf16 in words a and b. Where one of them is a NaN its code becomes
+// 0x7F | sign, found on the bf16 bits two at a time.
+__device__ inline uint32_t nan_codes(uint32_t a, uint32_t b, uint32_t q) {
+  const uint32_t na = ((a & 0x7FFF7FFFu) + 0x007F007Fu) & 0x80008000u;  // bit 15 / 31: that half is a NaN
+  const uint32_t nb = ((b & 0x7FFF7FFFu) + 0x007F007Fu) & 0x80008000u;
+  const uint32_t n = __builtin_amdgcn_perm(nb, na, 0x07050301u);              // one byte per element: 0x80 if NaN
+  const uint32_t s = __builtin_amdgcn_perm(b, a, 0x07050301u) & 0x80808080u;  // and its sign bit
+  const uint32_t m = (n >> 7) * 0xFFu;                                        // 0xFF if NaN
+  return (q & ~m) | (m & (0x7F7F7F7Fu | s));
+}
+
 template <int LANES>  // lanes per scale block (block / 8)
 __global__ void __launch_bounds__(256) fp8_pack_kernel(const uint4* __restrict__ in, int64_t nthreads,
                                                        uint2* __restrict__ out, float* __restrict__ scales) {
@@ -54,24 +65,33 @@ __global__ void __launch_bounds__(256) fp8_pack_kernel(const uint4* __restrict__
     x[2 * i + 1] = bf16_to_f32(uint16_t(w[i] >> 16));
   }
   float amax = 0.f;
+  bool special = false;  // an inf or a NaN among this thread's values
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (finite(x[i])) amax = fmaxf(amax, fabsf(x[i]));
+  for (int i = 0; i < 8; ++i) {
+    const bool f = finite(x[i]);
+    special |= !f;
+    if (f) amax = fmaxf(amax, fabsf(x[i]));
+  }
   amax = group_max<LANES>(amax);
   const int e = scale_exp(__float_as_uint(amax));
   const float inv = __uint_as_float(uint32_t(127 - e) << 23);  // 2^-E, E in [-126, 120]
   const float lim = e >= 120 ? 240.0f : 448.0f;                  // core/fp8.h sat_limit
+  // Saturate finite and infinite values. A NaN may come out as anything: its code is rewritten below.
   float y[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    y[i] = x[i] * inv;
-    // Saturate finite and infinite values; NaN is left for the converter (-> NaN).
-    if (y[i] == y[i]) y[i] = __builtin_amdgcn_fmed3f(y[i], lim, -lim);
-  }
+  for (int i = 0; i < 8; ++i) y[i] = __builtin_amdgcn_fmed3f(x[i] * inv, lim, -lim);
   int lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
   lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
   int hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
   hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+  // NaN -> 0x7F | the input's sign (core/fp8.h). Left to the hardware, the multiply and the
+  // converter give 0xFF for a NaN of either sign (measured on MI355X), and keeping NaNs out of
+  // v_med3 costs a compare and a select per element. NaNs are rare: threads without an inf or a
+  // NaN skip this branch.
+  if (special) {
+    lo = int(nan_codes(w[0], w[1], uint32_t(lo)));
+    hi = int(nan_codes(w[2], w[3], uint32_t(hi)));
+  }
   if (!active) return;
   // written once, read by a later pass or another GPU: nontemporal (profiles/r4_nt)
   using v2 = unsigned int __attribute__((ext_vector_type(2)));

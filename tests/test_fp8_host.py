@@ -1,9 +1,14 @@
-"""Host reference of the fp8 wire format (csrc/core/fp8.cc) against torch fp32/fp64 references.
+"""Host reference of the fp8 wire format (csrc/core/fp8.cc) against an independent numpy reference
+of the rules in core/fp8.h (integer and f64 arithmetic only: the e4m3fn value table, the scale
+formula on the f32 bits of the block's finite amax, a nearest-value search with ties to the even
+code, round-to-nearest-even to bf16 on the f32 bits), and against torch fp32/fp64 references.
 
 The format (core/fp8.h): per source chunk [e4m3fn codes][one f32 scale per block], the scale a
 power of two 2^E with E the smallest integer >= -126 such that the block's finite amax <= 448 * 2^E.
-The gfx950 kernels are checked against this host reference in test_gpu_kernels.py."""
+Every comparison with the numpy reference is exact equality. The gfx950 kernels are checked
+against the same reference and inputs in test_gpu_fp8.py."""
 import numpy as np
+import pytest
 import torch
 
 from distributed_llm_dissemination_amd import _core
@@ -11,6 +16,201 @@ from distributed_llm_dissemination_amd import _core
 from test_gpu_kernels import _fp8_reference, _scale_exp
 
 MiB = 1 << 20
+BLOCKS = (32, 64, 128, 256, 512)
+# the 127 e4m3fn magnitudes, code 0x00..0x7E: subnormals m * 2^-9, normals (1 + m/8) * 2^(e - 7)
+MAG = np.array([m * 2.0**-9 if e == 0 else (1 + m / 8) * 2.0**(e - 7) for e in range(16) for m in range(8)][:127])
+LADDER_E = (-126, -125, -118, -8, 0, 7, 119, 120)
+
+
+# ---------------------------------------------------------------- the reference
+
+def ref_scale_exp(amax_bf16):
+    """E from the bf16 bits of a block's finite amax (the rule is stated on its f32 bits)."""
+    ab = np.asarray(amax_bf16).astype(np.int64) << 16
+    ef, mant = ab >> 23, ab & 0x7FFFFF
+    e = ef - 135 + (mant > 0x600000)
+    e = np.where(ef == 0, -126, e)
+    e = np.maximum(e, -126)
+    return np.where(ab == 0, 0, e)
+
+
+def ref_pack(bits, block):
+    """bf16 bit patterns (uint16, a multiple of block) -> (q uint8 [n], scales float32 [n / block])."""
+    b = np.asarray(bits, dtype=np.uint16).reshape(-1, block).astype(np.uint32)
+    a = b & 0x7FFF
+    nan = a > 0x7F80
+    e = ref_scale_exp(np.where(a < 0x7F80, a, 0).max(1))  # bf16 magnitudes are monotonic in their bits
+    with np.errstate(all="ignore"):
+        x = np.where(nan, 0, a << 16).astype(np.uint32).view(np.float32).astype(np.float64)  # |x|, inf included
+        y = np.minimum(x * np.ldexp(1.0, -e)[:, None], np.where(e >= 120, 240.0, 448.0)[:, None])  # exact in f64
+    lo = np.searchsorted(MAG, y, side="right") - 1  # MAG[lo] <= y <= MAG[hi]
+    hi = np.minimum(lo + 1, 126)
+    dl, dh = y - MAG[lo], MAG[hi] - y  # exact wherever they can be equal (y has 8 significant bits)
+    code = np.where(dl < dh, lo, np.where(dh < dl, hi, np.where(lo % 2 == 0, lo, hi)))
+    code = np.where(nan, 0x7F, code) | ((b >> 15) << 7)
+    return code.astype(np.uint8).reshape(-1), np.ldexp(1.0, e).astype(np.float32)
+
+
+def ref_unpack(q, scales, block):
+    """(q uint8 [n], scales float32 [n / block]) -> bf16 bit patterns uint16 [n]; a NaN code gives a NaN."""
+    q = np.asarray(q, dtype=np.uint8).reshape(-1, block)
+    mag = np.append(MAG, 0.0)[q & 0x7F]
+    v = np.where(q & 0x80, -1.0, 1.0) * mag * np.asarray(scales, dtype=np.float32).astype(np.float64)[:, None]
+    with np.errstate(over="ignore"):
+        u = v.astype(np.float32).view(np.uint32).astype(np.uint64)  # exact (>= 2^-135), or inf beyond f32
+    out = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)  # round to nearest even on the f32 bits
+    out = np.where((q & 0x7F) == 0x7F, 0x7FC0 | ((q.astype(np.uint16) & 0x80) << 8), out).astype(np.uint16)
+    return out.reshape(-1)
+
+
+def is_nan(bits):
+    return (np.asarray(bits) & 0x7FFF) > 0x7F80
+
+
+def assert_bf16_equal(got, want):
+    """Bit for bit, except that any NaN matches any NaN (payloads may differ)."""
+    got, want = np.asarray(got).view(np.uint16), np.asarray(want).view(np.uint16)
+    assert got.shape == want.shape
+    assert np.array_equal(is_nan(got), is_nan(want))
+    bad = np.nonzero((got != want) & ~is_nan(want))[0]
+    assert len(bad) == 0, (len(bad), [(int(i), hex(got[i]), hex(want[i])) for i in bad[:8]])
+
+
+# ---------------------------------------------------------------- inputs
+
+def bf16_bits(values):
+    """bf16 bit patterns of values that are exactly representable in bf16."""
+    f = np.asarray(values, dtype=np.float64).astype(np.float32)
+    u = f.view(np.uint32)
+    assert not (u & 0xFFFF).any() and np.array_equal(f.astype(np.float64), np.asarray(values, dtype=np.float64))
+    return (u >> 16).astype(np.uint16)
+
+
+def pow2_bits(p):
+    """bf16 bits of 2^p, p >= -133."""
+    return (p + 127) << 7 if p >= -126 else 1 << (p + 133)
+
+
+def top_bits(e):
+    """bf16 bits of the largest amax with scale exponent e: 448 * 2^e, the bf16 maximum at e = 120."""
+    return 0x7F7F if e == 120 else ((e + 135) << 7) | 0x60
+
+
+def all_patterns(block=32):
+    return np.arange(65536, dtype=np.uint32).astype(np.uint16)
+
+
+def permuted_patterns(block=32):
+    return all_patterns()[np.random.default_rng(20240611).permutation(65536)]
+
+
+def ladder(block):
+    """Per E of LADDER_E: blocks with the amax element 448 * 2^E at position (37 b) % block, of
+    alternating sign; the other elements run through every bf16 magnitude from 2^max(E - 11, -133)
+    up to the amax in both signs (the last block wraps round to the first ones), so every
+    y = |x| * 2^-E in [2^-11, 448] that a bf16 can give meets the converter at a known scale."""
+    out = []
+    for e in LADDER_E:
+        m = np.arange(pow2_bits(max(e - 11, -133)), top_bits(e) + 1, dtype=np.uint32)
+        vals = np.stack([m, m | 0x8000], 1).reshape(-1)
+        nb = -(-len(vals) // (block - 1))
+        vals = np.resize(vals, nb * (block - 1)).reshape(nb, block - 1)
+        blk = np.empty((nb, block), dtype=np.uint32)
+        for b in range(nb):
+            blk[b] = np.insert(vals[b], (37 * b) % block, top_bits(e) | (0x8000 if b % 2 else 0))
+        out.append(blk.reshape(-1))
+    return np.concatenate(out).astype(np.uint16)
+
+
+def amax_position(block):
+    """`block` blocks of 1.0: block p holds +-450 (E = 1) at position p and -+inf, which the amax
+    must ignore and the converter saturate to -+448, at position p + 1."""
+    x = np.full((block, block), 0x3F80, dtype=np.uint16)
+    for p in range(block):
+        x[p, p] = 0x43E1 | (0x8000 if p % 2 else 0)
+        if p + 1 < block:
+            x[p, p + 1] = 0xFF80 if p % 3 else 0x7F80
+    return x.reshape(-1)
+
+
+def handmade(block):
+    blocks = []
+
+    def blk(head, fill=0):
+        v = np.full(block, fill, dtype=np.uint16)
+        v[: len(head)] = head
+        blocks.append(np.roll(v, 5 * len(blocks)))  # the head starts at another lane in every block
+
+    blk([], 0x0000)                                     # all zero
+    blk([], 0x8000)                                     # all -0
+    blk([], 0x7FC0)                                     # all NaN
+    blk([0xFFFF, 0x7F81, 0xFFC0, 0x7FFF, 0xFF81], 0x7FC0)  # NaN payloads of both signs
+    blk([0xFFC0, 0x7F81], 0xFFFF)
+    blk(np.r_[bf16_bits([1, -2, 3.5, 0.1015625]), [0x7FC1, 0xFFC1]], 0x3F80)  # NaNs among finite values
+    blk([0x7F80, 0xFF80] * 16, 0xFF80)                  # all +-inf: E = 0, codes +-448
+    blk(np.r_[[0x7F80, 0xFF80], bf16_bits([1, -3, 0.25, 100])])  # inf beside finite values
+    blk(np.arange(1, 33), 1)                            # only subnormals (E = -126)
+    blk(np.arange(0x60, 0x80) | 0x8000, 0x8001)         # negative subnormals, the largest ones
+    for k in (-134, -126, -9, 0, 119):
+        top = bf16_bits([448 * 2.0**k])[0]
+        rest = bf16_bits([v * 2.0**k for v in (-400, 224, 8, -24, 64, 176, 288, -448, 232, -2)])
+        blk(np.r_[[top], rest])                         # amax exactly 448 * 2^k
+        blk(np.r_[[top + 1], rest])                     # one ulp above: E = k + 1
+        blk(np.r_[[top | 0x8000], rest], 0x8000)
+        blk(np.r_[[(top + 1) | 0x8000], rest], 0x8000)
+    # bf16 max: E = 120, values in (240, 448] * 2^120 clamp to code 0x77 (240)
+    blk([0x7F7F, 0xFF7F, 0x7F71, 0xFF71, 0x7F70, 0x7F78, 0xFF78, 0x7F60, 0x7F6F, 0x7F00, 0xFE80, 0x7F80, 0xFF80])
+    blk(np.r_[[0x7F62], bf16_bits([1, -1])])            # just above 448 * 2^119: E = 120 too
+    # amax 448 (E = 0): -2^-12 and -2^-11 are below half the smallest code, -2^-10 is the tie
+    # with it (to even: zero); all keep their sign as code 0x80
+    blk(np.r_[bf16_bits([448, -2.0**-12, -2.0**-11, -2.0**-10, 2.0**-10, -1.5 * 2.0**-10]), ], bf16_bits([-2.0**-12])[0])
+    return np.concatenate(blocks)
+
+
+CASES = {"natural": all_patterns, "permuted": permuted_patterns, "ladder": ladder, "amax_position": amax_position,
+         "handmade": handmade}
+
+
+def every_code_and_scale(block):
+    """All 256 codes times every E in [-126, 120]: 2048 elements per E (8 rotated runs of the 256
+    codes). Returns (q, scales, exact): `exact` is False for the 14 codes +-0x78..0x7E at E = 120,
+    which pack never writes and whose product overflows bf16 (core/fp8.h: unspecified)."""
+    es = np.arange(-126, 121)
+    q = np.stack([np.roll(np.arange(256), 37 * r) for r in range(8)]).reshape(-1).astype(np.uint8)
+    q = np.tile(q, len(es))
+    scales = np.repeat(np.ldexp(1.0, es).astype(np.float32), 2048 // block)
+    exact = ~((np.repeat(es, 2048) == 120) & ((q & 0x7F) >= 0x78) & ((q & 0x7F) <= 0x7E))
+    return q, scales, exact
+
+
+def out_of_format(block):
+    """The pairs every_code_and_scale leaves out: codes +-0x78..0x7E at E = 120."""
+    codes = np.r_[np.arange(0x78, 0x7F), np.arange(0xF8, 0xFF)]
+    q = np.resize(codes, 2 * block).astype(np.uint8)
+    return q, np.full(2, 2.0**120, dtype=np.float32)
+
+
+def host_pack(bits, block):
+    """The host codec on one chunk: (q, scales)."""
+    n = len(bits)
+    packed = _core.fp8_pack_layer_host(np.asarray(bits, dtype=np.uint16).tobytes(), 2 * n, block)
+    assert len(packed) == n + n // block * 4
+    return np.frombuffer(packed, dtype=np.uint8, count=n), np.frombuffer(packed, dtype=np.float32, offset=n)
+
+
+def host_unpack(q, scales, block):
+    n = len(q)
+    packed = np.asarray(q, dtype=np.uint8).tobytes() + np.asarray(scales, dtype=np.float32).tobytes()
+    return np.frombuffer(_core.fp8_unpack_layer_host(packed, 2 * n, 2 * n, block), dtype=np.uint16)
+
+
+def chunked_image(q, scales, block, chunk):
+    """[q][scales] per source chunk of `chunk` bytes, laid end to end (core/fp8.h)."""
+    n = chunk // 2
+    parts = []
+    for o in range(0, len(q), n):
+        parts += [q[o: o + n].tobytes(), scales[o // block: (o + n) // block].tobytes()]
+    return b"".join(parts)
 
 
 def _split(packed: bytes, src: int, chunk: int, block: int):
@@ -57,7 +257,8 @@ def test_host_unpack_is_exact_product():
     y = torch.from_numpy(np.frombuffer(out, dtype=np.uint8).copy()).view(torch.bfloat16)
     q, s = _split(packed, src, chunk, block)
     want = (q.view(torch.float8_e4m3fn).double().view(-1, block) * s.double()[:, None]).view(-1)
-    # a power-of-two scale times an e4m3 value is exact in bf16 (3 mantissa bits < 8)
+    # a power-of-two scale times an e4m3 value is exact in bf16 (3 mantissa bits < 8) at these
+    # scales; E <= -125: test_host_unpack_every_code_and_scale
     assert torch.equal(y.double(), want)
     err = (y.float() - x.float()).abs()
     assert bool((err <= x.float().abs() * 2**-4 + s.repeat_interleave(block) * 2**-9).all())
@@ -81,3 +282,77 @@ def test_host_roundtrip_random_bit_patterns():
     assert bool(((err <= x.abs() * 0.0625 + s.repeat_interleave(block) * 2**-9) | ~fin).all())
     inf = torch.isinf(x)
     assert torch.equal(y[inf].sign(), x[inf].sign())
+
+
+# ---------------------------------------------------------------- host codec against the numpy reference
+
+def test_reference_rules():
+    """The reference itself on hand-computed values of the format's description."""
+    amax = bf16_bits([0, 448, 450, 224, 1, 2.0**-130, 448 * 2.0**-126, 450 * 2.0**-126, 448 * 2.0**-134,
+                      448 * 2.0**119, 450 * 2.0**119])
+    assert ref_scale_exp(np.r_[amax, [0x7F7F]]).tolist() == [0, 0, 1, -1, -8, -126, -126, -125, -126, 119, 120, 120]
+    assert MAG[[0, 1, 7, 8, 0x38, 0x76, 0x77, 0x78, 0x7E]].tolist() == [0, 2.0**-9, 7 * 2.0**-9, 2.0**-6, 1, 224, 240, 256, 448]
+    # E = 0: ties go to the even code (232 -> 224, 248 -> 256, 2^-10 -> 0, 3 * 2^-10 -> 2 * 2^-9),
+    # zeros keep their sign, inf saturates, NaN keeps its sign
+    x = np.zeros(32, dtype=np.uint16)
+    x[:14] = np.r_[bf16_bits([448, 232, -248, 2.0**-10, -2.0**-10, 3 * 2.0**-10, 1.0625, -1.1875, 436, 0.0]),
+                   [0x8000, 0xFF80, 0x7FC0, 0xFFC1]]
+    q, s = ref_pack(x, 32)
+    assert s.tolist() == [1.0]
+    assert q[:14].tolist() == [0x7E, 0x76, 0xF8, 0x00, 0x80, 0x02, 0x38, 0xBA, 0x7E, 0x00, 0x80, 0xFE, 0x7F, 0xFF]
+    # E = 120: the limit is 240; E = -126: a subnormal amax
+    x = np.zeros(64, dtype=np.uint16)
+    x[:4] = [0x7F7F, 0xFF78, 0x7F70, 0x7F60]
+    x[32:35] = [0x0001, 0x807F, 0x0040]
+    q, s = ref_pack(x, 32)
+    assert s.tolist() == [2.0**120, 2.0**-126]
+    assert q[:4].tolist() == [0x77, 0xF7, 0x77, 0x76] and q[32:35].tolist() == [0x04, 0xB8, 0x30]  # 2^-7, -127/128, 1/2
+    # unpack: exact products, and the two lowest scales round to bf16's subnormal grid (step 2^-133)
+    qq = np.zeros(96, dtype=np.uint8)
+    qq[:4] = [0x7E, 0xB8, 0x01, 0x77]
+    qq[32:39] = [0x01, 0x02, 0x03, 0x83, 0x05, 0x06, 0x08]
+    qq[64:68] = [0x01, 0x02, 0x03, 0x7F]
+    out = ref_unpack(qq, np.array([2.0**120, 2.0**-126, 2.0**-125], dtype=np.float32), 32)
+    assert out[:4].tolist() == [0x7F80, 0xFB80, bf16_bits([2.0**111])[0], 0x7F70]
+    # 2^-135 -> 0, 2 * 2^-135 is the tie of 0 and 2^-133 -> 0, 3 * 2^-135 -> 2^-133, 5 -> 1, 6 -> tie of 1 and 2 -> 2
+    assert out[32:39].tolist() == [0, 0, 1, 0x8001, 1, 2, 2]
+    assert out[64:67].tolist() == [0, 1, 2] and is_nan(out[67])  # 2^-134 is the tie of 0 and 1; 3 * 2^-134 of 1 and 2
+
+
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("block", BLOCKS)
+def test_host_pack_matches_reference(block, case):
+    bits = CASES[case](block)
+    q, s = host_pack(bits, block)
+    qr, sr = ref_pack(bits, block)
+    assert np.array_equal(s.view(np.uint32), sr.view(np.uint32))
+    assert np.array_equal(q, qr)
+    e = (s.view(np.uint32) >> 23).astype(int) - 127
+    assert not (s.view(np.uint32) & 0x807FFFFF).any() and e.min() >= -126 and e.max() <= 120
+
+
+@pytest.mark.parametrize("case", list(CASES))
+@pytest.mark.parametrize("block", BLOCKS)
+def test_host_unpack_matches_reference(block, case):
+    bits = CASES[case](block)
+    q, s = ref_pack(bits, block)
+    out = host_unpack(q, s, block)
+    assert_bf16_equal(out, ref_unpack(q, s, block))
+    assert not ((out & 0x7FFF) == 0x7F80).any()  # nothing packed unpacks to inf
+    assert np.array_equal(is_nan(out), is_nan(bits))
+    assert set(out[is_nan(out)].tolist()) <= {0xFFC0}  # the converter's NaN, for codes 0x7F and 0xFF (core/fp8.h)
+
+
+@pytest.mark.parametrize("block", BLOCKS)
+def test_host_unpack_every_code_and_scale(block):
+    q, s, exact = every_code_and_scale(block)
+    assert len(np.unique(q.astype(np.int64) * 512 + np.repeat(s.view(np.uint32) >> 23, block))) == 256 * 247
+    out, want = host_unpack(q, s, block), ref_unpack(q, s, block)
+    assert_bf16_equal(out[exact], want[exact])
+    assert (~exact).sum() == 14 * 8
+    # the products that are no multiple of bf16's smallest subnormal, 2^-133, and are rounded: 48 pairs
+    # at E = -126 and -125 (core/fp8.h); every other product is exact
+    steps = np.append(MAG, 0.0)[q & 0x7F] * np.repeat(s, block).astype(np.float64) * 2.0**133
+    rounded = steps != np.floor(steps)
+    pairs = np.unique(q[rounded].astype(np.int64) * 512 + np.repeat(s.view(np.uint32) >> 23, block)[rounded])
+    assert len(pairs) == 48 and set(pairs % 512) == {1, 2}

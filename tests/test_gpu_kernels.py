@@ -1,6 +1,5 @@
 """gfx950 kernel numerics vs host / PyTorch fp32 references."""
 
-import numpy as np
 import pytest
 import torch
 
@@ -239,20 +238,11 @@ def test_fp8_pack_matches_torch(gpu, block):
     torch.cuda.synchronize()
     qr, sr = _fp8_reference(x.cpu(), block)
     torch.testing.assert_close(s.cpu(), sr, rtol=0, atol=0)
-    qg = q.cpu()
-    bad = (qg != qr).nonzero().flatten()
-    # gfx950's v_cvt_pk_fp8_f32 double-rounds values within ~2^-20 of a rounding tie
-    # (e.g. 168.0000153 -> 160 instead of 176): the code may then be the other
-    # neighbor. Everything else must match IEEE round-to-nearest-even exactly.
-    xf = x.float().cpu().view(-1, block)
-    y = (xf / sr[:, None]).flatten()
-    dec = lambda c: c.view(torch.float8_e4m3fn).float()  # noqa: E731
-    for i in bad.tolist():
-        a, b = dec(qg[i : i + 1]).item(), dec(qr[i : i + 1]).item()
-        tie = 0.5 * (a + b)
-        assert abs(int(qg[i]) - int(qr[i])) == 1, (float(y[i]), int(qg[i]), int(qr[i]))
-        assert abs(float(y[i]) - tie) <= abs(tie) * 2**-18, (float(y[i]), a, b)
-    assert len(bad) < n * 0.002
+    # gfx950's v_cvt_pk_fp8_f32 double-rounds general f32 values within ~2^-18 of a rounding
+    # tie (168.0000153 -> 160 instead of 176). A bf16 times 2^-E has 8 significant bits: it is
+    # on a tie or far from one, so every code matches IEEE round-to-nearest-even
+    # (test_gpu_fp8.py: every such value, at every scale).
+    assert torch.equal(q.cpu(), qr)
 
 
 def test_fp8_roundtrip_random_bit_patterns(gpu):
@@ -280,18 +270,6 @@ def test_fp8_roundtrip_random_bit_patterns(gpu):
     assert torch.equal(yf[inf].sign(), xf[inf].sign())
 
 
-def _host_fp8_codes_close(got: bytes, want: bytes, n_q_per_chunk, pchunk):
-    """q codes may differ by one near rounding ties (gfx950 double rounding); scales must match."""
-    g = np.frombuffer(got, dtype=np.uint8)
-    w = np.frombuffer(want, dtype=np.uint8)
-    assert g.shape == w.shape
-    diff = np.nonzero(g != w)[0]
-    in_q = (diff % pchunk) < n_q_per_chunk(diff // pchunk)
-    assert in_q.all(), "scale bytes differ"
-    assert (np.abs(g[diff].astype(int) - w[diff].astype(int)) == 1).all()
-    assert len(diff) < g.size * 0.002
-
-
 @pytest.mark.parametrize("size,chunk,block", [(3 * (1 << 20) + 4096, 1 << 20, 128), (2 << 20, 1 << 20, 32),
                                               ((1 << 20) + 1024, 64 << 10, 512)])
 def test_fp8_pack_chunks_matches_host_layout(gpu, size, chunk, block):
@@ -301,13 +279,9 @@ def test_fp8_pack_chunks_matches_host_layout(gpu, size, chunk, block):
     gpu.fp8_pack_chunks(x.data_ptr(), size, chunk, block, out.data_ptr())
     torch.cuda.synchronize()
     want = gpu.fp8_pack_layer_host(x.view(torch.uint8).cpu().numpy().tobytes(), chunk, block)
-    pchunk = chunk // 2 + chunk // 2 // block * 4
-    last_q = (size % chunk) // 2 if size % chunk else chunk // 2
-
-    def n_q(c):
-        return np.where(c == (packed_n - 1) // pchunk, last_q, chunk // 2)
-
-    _host_fp8_codes_close(out.cpu().numpy().tobytes(), want, n_q, pchunk)
+    # codes and scales byte for byte: the hardware's double rounding near ties needs more
+    # significant bits than a scaled bf16 has (core/fp8.h)
+    assert out.cpu().numpy().tobytes() == want
 
 
 def _torch_unpack(packed: torch.Tensor, src_len: int, block: int) -> torch.Tensor:
@@ -330,7 +304,8 @@ def _assert_bf16_bits_equal(got: torch.Tensor, want: torch.Tensor):
 @pytest.mark.parametrize("block", [32, 128, 512])
 def test_fp8_unpack_matches_torch_fp32(gpu, block):
     """The standalone unpack kernel against the fp32 torch reference, on random
-    bit patterns packed by the kernel (NaN codes and every scale exponent)."""
+    bit patterns packed by the kernel (NaN codes; random exponents give scales of about
+    2^100 to 2^120 only - every exponent from -126 is in test_gpu_fp8.py)."""
     size, chunk = 4 << 20, 4 << 20
     raw = _dev_bytes(size)
     gpu.fill_random(raw.data_ptr(), size, 31 + block)
