@@ -578,6 +578,17 @@ PYBIND11_MODULE(_core, m) {
     }
     return py::bytes(out);
   }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"));
+  // elements [elem_off, elem_off + n) of a packed layer in host memory at `packed` -> n bf16 at `out`
+  m.def("mxfp4_unpack_range_host", [](uint64_t packed, int64_t packed_bytes, int64_t src_bytes, int64_t src_chunk,
+                                      int64_t elem_off, int64_t n, uint64_t out) {
+    mxfp4::check(src_bytes, src_chunk);
+    if (packed_bytes < mxfp4::packed_size(src_bytes, src_chunk))
+      throw std::runtime_error("packed buffer is smaller than the layer's packed size");
+    py::gil_scoped_release nogil;
+    mxfp4::unpack_range_host(reinterpret_cast<const uint8_t*>(packed), src_bytes, src_chunk, elem_off, n,
+                             reinterpret_cast<uint16_t*>(out));
+  }, py::arg("packed"), py::arg("packed_bytes"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"),
+     py::arg("n"), py::arg("out"));
 
   // ---- roles
   py::class_<NodeConfig>(m, "NodeConfig")

@@ -107,5 +107,31 @@ void unpack_layer_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chu
   }
 }
 
+void unpack_range_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, int64_t n,
+                       uint16_t* out) {
+  check(src_bytes, src_chunk);
+  const int64_t total = src_bytes / 2, ce = src_chunk / 2;
+  if (elem_off < 0 || n < 0 || elem_off > total || n > total - elem_off)
+    throw std::runtime_error("mxfp4 element range lies outside the layer");
+  for (int64_t e = elem_off, end = elem_off + n; e < end;) {
+    const int64_t c = e / ce, r = e - c * ce;
+    const int64_t nc = std::min(ce, total - c * ce);  // elements of this chunk
+    const int64_t take = std::min(end - e, nc - r);
+    const uint8_t* q = packed + c * packed_chunk(src_chunk);
+    const uint8_t* scales = q + nc / 2;
+    uint16_t* o = out + (e - elem_off);
+    for (int64_t i = r; i < r + take; ++i) {
+      const uint8_t s = scales[i / kBlock];
+      if (s == kNanScale) {
+        o[i - r] = 0x7FC0;
+        continue;
+      }
+      const uint8_t code = (q[i / 2] >> (4 * (i & 1))) & 15;
+      o[i - r] = exact_f32_to_bf16(std::ldexp(e2m1_to_f32(code), int(s) - 127));
+    }
+    e += take;
+  }
+}
+
 }  // namespace mxfp4
 }  // namespace dissem

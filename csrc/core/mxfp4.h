@@ -37,6 +37,13 @@
 // Unpack: value[m] * 2^(byte - 127) with the sign is exactly representable in
 // bf16, subnormals included (byte 0 scales by 2^-127).
 //
+// As an MFMA operand: measured once on MI355X through kernels/mxfp4_linear.hip,
+// v_mfma_f32_16x16x32_bf16 keeps bf16-subnormal operands and f32-subnormal
+// sums - weights of 2^-127 (scale byte 0) times x = 2^120 over K = 32 gave
+// exactly 0.25, x = 2^-130 times weights of 2^123 likewise, and 32 * 2^-136
+// came out as 2^-131 - so the smallest scales are not flushed there. No test
+// asserts it (the instruction's denormal handling is not documented).
+//
 // The host functions below define the format; the gfx950 kernels
 // (kernels/mxfp4.hip, the fused check in kernels/crc32c.hip) produce the same
 // bytes.
@@ -95,6 +102,12 @@ void unpack_host(const uint8_t* q, const uint8_t* scales, int64_t n, uint16_t* b
 // Whole layer: src_bytes of bf16 -> packed_size(...) bytes in the chunked layout.
 void pack_layer_host(const uint8_t* src, int64_t src_bytes, int64_t src_chunk, uint8_t* dst);
 void unpack_layer_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chunk, uint8_t* dst);
+// Elements [elem_off, elem_off + n) of a chunked packed layer -> n bf16: the one
+// definition of where an element of the layer lives (chunk e / (src_chunk / 2),
+// code and scale block at its offset in that chunk, the tail chunk on its own
+// length). Any offset and length inside the layer; throws otherwise.
+void unpack_range_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, int64_t n,
+                       uint16_t* out);
 
 }  // namespace mxfp4
 }  // namespace dissem

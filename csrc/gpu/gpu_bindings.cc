@@ -484,6 +484,18 @@ void register_gpu_bindings(PyObject* module) {
     check(kern::mxfp4_verify_unpack_batch(v.data(), int(v.size()), reinterpret_cast<void*>(ws), as_stream(stream), cus),
           "mxfp4_verify_unpack_batch");
   }, py::arg("items"), py::arg("crc_out"), py::arg("ws"), py::arg("stream") = 0, py::arg("cus") = 0);
+  // W4A16 linear from the packed layer in place (kernels/mxfp4_linear.hip); stream-ordered
+  m.def("mxfp4_linear", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,
+                           int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16, int split_k,
+                           int row_tiles, uint64_t stream) {
+    check(kern::mxfp4_linear(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, elem_off,
+                             reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                             y_bf16, split_k, row_tiles, as_stream(stream)),
+          "mxfp4_linear");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"), py::arg("x"), py::arg("m"),
+     py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"), py::arg("split_k") = 0,
+     py::arg("row_tiles") = 0, py::arg("stream") = 0);
+  m.def("mxfp4_linear_slices", &kern::mxfp4_linear_slices, py::arg("m"), py::arg("n"), py::arg("k"));
 
   // ---- RCCL path on one GPU: a one-rank communicator driven through the same
   // Backend::group / crc calls the planned engine issues. `rounds` groups of

@@ -99,5 +99,24 @@ hipError_t mxfp4_verify_unpack(const void* packed, int64_t src_bytes, int64_t sr
                                uint32_t* crc_out, void* workspace, hipStream_t s, int cus = 0);
 hipError_t mxfp4_verify_unpack_batch(const FusedItem* items, int n, void* workspace, hipStream_t s, int cus = 0);
 
+// ---- mxfp4_linear.hip: y[m][n] = sum_k x[m][k] * W[n][k] with W read in place
+// from an MXFP4-packed layer (no bf16 copy of W): W is a row-major [N, K]
+// parameter whose element 0 is element `elem_off` of the layer of `src_bytes`
+// stored at `packed` in the chunked layout of core/mxfp4.h. x: bf16 [M, K],
+// contiguous, 16-B aligned; y: f32 or bf16 [M, N] with a row stride of `ldy`
+// elements; f32 accumulation (v_mfma_f32_16x16x32_bf16). K, elem_off multiples
+// of 32, N of 16, M >= 1, the parameter inside the layer; `packed` 16-B aligned.
+// Anything else: hipErrorInvalidValue. Stream-ordered, no allocation, no
+// workspace: K is split over the waves of a workgroup (`split_k` of them, 1..16;
+// 0 = chosen from the shape, mxfp4_linear_slices) and reduced through LDS in a
+// fixed order, so equal inputs give equal bits. `row_tiles_per_wave` (0 =
+// chosen from the shape; 1, 2 or 4, a divisor of N / 16; at most 2 beyond 32
+// rows of x): the 16-row tiles of W a wave feeds from one x fragment. Rows of x
+// beyond 64 are served by further passes over W.
+int mxfp4_linear_slices(int64_t M, int64_t N, int64_t K);
+hipError_t mxfp4_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, const uint16_t* x,
+                        int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
+                        int row_tiles_per_wave, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

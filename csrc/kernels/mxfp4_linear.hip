@@ -1,0 +1,326 @@
+// W4A16 linear, y = x * W^T, with W read in place from an MXFP4-packed layer
+// (core/mxfp4.h): bf16 activations, e2m1 weights dequantized in registers by
+// v_cvt_scalef32_pk_bf16_fp4 (mxfp4_cvt.h), f32 accumulation in
+// v_mfma_f32_16x16x32_bf16. No bf16 copy of W exists anywhere, and W never
+// passes through LDS: global -> registers -> MFMA operand.
+//
+// Fragment maps of v_mfma_f32_16x16x32_bf16 (lane l, c = l & 15, g = l >> 4):
+//   A[row c][k = 8g + j], B[k = 8g + j][col c], j = 0..7;  D[row 4g + i][col c], i = 0..3.
+// With A = x (rows m) and B = W^T (columns n), lane l's B fragment is 8
+// consecutive k of weight row n0 + c: one dword of q, and one 32-element scale
+// block is one K = 32 step of one row.
+//
+// Main loop, K in steps of 128: a lane takes a whole scale block - 16 B of q
+// and one scale byte, block 4 * step + g of its row - and feeds its four dwords
+// to four consecutive MFMAs. In MFMA t the k slot 8g + j therefore stands for
+// k = 128 step + 32g + 8t + j; a sum over k is order-free, so the x fragment
+// follows the same order (16 B at x[m][128 step + 32g + 8t]). The K tail
+// (K % 128 != 0) runs one block per MFMA in the plain order, 4 B of q per lane.
+//
+// Position in the chunked layout: a row may start anywhere on the 32-element
+// grid and straddle source chunks (or end in the short tail chunk). Each lane
+// keeps {chunk base, block index in the chunk, blocks of the chunk}; it is
+// computed once per wave with one 64-bit division and then advanced by 4 blocks
+// with a wrap. A chunk holds at least 16 blocks, so one wrap per advance suffices.
+//
+// Work: one workgroup per 16 * NT weight rows (NT = 1, 2 or 4 row tiles per
+// wave, all fed from one x fragment: x comes through L1/L2, and at 16 rows of
+// x a single row tile would read four times as many x bytes as weight bytes).
+// The waves of a workgroup split K (in steps of 128) and reduce through LDS in
+// the fixed order of the slices, so the result does not depend on timing - no
+// floating-point atomics. A wave keeps up to 4 accumulator tiles along M (64
+// rows of x) per pass over its weights; the launcher makes one pass per 64 rows.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kernels/kernels.h"
+#include "kernels/mxfp4_cvt.h"
+
+namespace dissem {
+namespace kern {
+
+namespace {
+
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+
+struct Mxfp4Layout {
+  const uint8_t* packed;
+  int64_t pchunk;  // bytes of a full packed chunk
+  int64_t full;    // full chunks of the layer
+  int cblk;        // scale blocks of a full chunk
+  int tblk;        // scale blocks of the tail chunk (0: none)
+};
+
+// One lane's place in the packed layer, in scale blocks.
+struct BlockPos {
+  const uint8_t* base;  // the chunk
+  int64_t c;            // its index
+  int r;                // block within the chunk
+  int nblk;             // blocks of the chunk: q is 16 * nblk bytes, the scales follow
+  __device__ __forceinline__ void init(const Mxfp4Layout& L, int64_t block) {
+    c = block / L.cblk;
+    r = int(block - c * L.cblk);
+    base = L.packed + c * L.pchunk;
+    nblk = c < L.full ? L.cblk : L.tblk;
+  }
+  // d <= 16 blocks forward. Past the end of the layer the position is
+  // meaningless; the callers never read through such a position.
+  __device__ __forceinline__ void advance(const Mxfp4Layout& L, int d) {
+    r += d;
+    if (r >= nblk) {
+      r -= nblk;
+      ++c;
+      base += L.pchunk;
+      nblk = c < L.full ? L.cblk : L.tblk;
+    }
+  }
+  __device__ __forceinline__ const uint8_t* q() const { return base + int64_t(r) * 16; }
+  __device__ __forceinline__ uint32_t scale() const { return base[int64_t(nblk) * 16 + r]; }
+};
+
+__device__ __forceinline__ bf16x8_t as_frag(const uint32_t (&o)[4]) {
+  return __builtin_bit_cast(bf16x8_t, u32x4_t{o[0], o[1], o[2], o[3]});
+}
+
+__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0x7FC0;
+  return uint16_t((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <bool BF16>
+__device__ __forceinline__ void store_y(void* y, int64_t idx, float v) {
+  if (BF16) static_cast<uint16_t*>(y)[idx] = f32_to_bf16_rne(v);
+  else static_cast<float*>(y)[idx] = v;
+}
+
+// MT: 16-row tiles of x in this pass (M <= 16 * MT); NT: 16-row tiles of W per
+// wave. blockDim.x = 64 * (K slices).
+template <int MT, int NT, bool BF16>
+__global__ void __launch_bounds__(MT * NT <= 2 ? 1024 : 512)
+    mxfp4_linear_kernel(Mxfp4Layout L, int64_t elem_off, const uint16_t* __restrict__ x, int M, int K,
+                        void* __restrict__ y, int64_t ldy) {
+  extern __shared__ float red[];  // [slice][MT * NT * 4][64], only with more than one slice
+  constexpr int T = MT * NT;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slices = blockDim.x >> 6;
+  const int c = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * (16 * NT);
+  const int nsteps = K >> 7, tail = (K >> 5) & 3;
+  const int per = (nsteps + slices - 1) / slices;
+  const int s0 = min(wave * per, nsteps), s1 = min(s0 + per, nsteps);
+  // first block of this lane's weight row in tile 0 (elem_off and K are
+  // multiples of 32); tile j is 16 rows = K / 2 blocks further
+  const int64_t row_blk = (elem_off + int64_t(n0 + c) * K) >> 5;
+  const int64_t tile_blk = int64_t(K) >> 1;
+
+  f32x4_t acc[MT][NT];
+  const uint16_t* xrow[MT];  // this lane's row of x per tile; rows past M read nothing
+  bool live[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) acc[t][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    live[t] = 16 * t + c < M;
+    xrow[t] = x + int64_t(live[t] ? 16 * t + c : 0) * K;
+  }
+  const u32x4_t zero4 = {0u, 0u, 0u, 0u};
+
+  if (s0 < s1) {
+    BlockPos pos[NT];
+    u32x4_t qn[NT];
+    uint32_t sn[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      pos[j].init(L, row_blk + j * tile_blk + 4 * int64_t(s0) + g);
+      qn[j] = *reinterpret_cast<const u32x4_t*>(pos[j].q());
+      sn[j] = pos[j].scale();
+    }
+    for (int s = s0; s < s1; ++s) {
+      u32x4_t qv[NT];
+      uint32_t sb[NT];
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        qv[j] = qn[j];
+        sb[j] = sn[j];
+      }
+      if (s + 1 < s1) {  // the next step's weights are in flight during this one
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          pos[j].advance(L, 4);
+          qn[j] = *reinterpret_cast<const u32x4_t*>(pos[j].q());
+          sn[j] = pos[j].scale();
+        }
+      }
+      const int k = (s << 7) + (g << 5);
+      u32x4_t a[MT][4];
+#pragma unroll
+      for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          a[t][u] = live[t] ? *reinterpret_cast<const u32x4_t*>(xrow[t] + k + 8 * u) : zero4;
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          uint32_t o[4];
+          mxfp4_unpack8(qv[j][u], sb[j], o);
+          const bf16x8_t b = as_frag(o);
+#pragma unroll
+          for (int t = 0; t < MT; ++t)
+            acc[t][j] =
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[t][u]), b, acc[t][j], 0, 0, 0);
+        }
+    }
+  }
+  if (tail && wave == slices - 1) {  // K % 128: one block per MFMA, 4 B of q per lane
+    BlockPos pos[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) pos[j].init(L, row_blk + j * tile_blk + 4 * int64_t(nsteps));
+    for (int tb = 0; tb < tail; ++tb) {
+      const int k = ((4 * nsteps + tb) << 5) + 8 * g;
+      u32x4_t a[MT];
+#pragma unroll
+      for (int t = 0; t < MT; ++t) a[t] = live[t] ? *reinterpret_cast<const u32x4_t*>(xrow[t] + k) : zero4;
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const uint32_t w = *reinterpret_cast<const uint32_t*>(pos[j].q() + 4 * g);
+        const uint32_t sb = pos[j].scale();
+        uint32_t o[4];
+        mxfp4_unpack8(w, sb, o);
+        const bf16x8_t b = as_frag(o);
+#pragma unroll
+        for (int t = 0; t < MT; ++t)
+          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a[t]), b, acc[t][j], 0, 0, 0);
+        if (tb + 1 < tail) pos[j].advance(L, 1);
+      }
+    }
+  }
+
+  if (slices == 1) {
+#pragma unroll
+    for (int t = 0; t < MT; ++t)
+#pragma unroll
+      for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int m = 16 * t + 4 * g + i;
+          if (m < M) store_y<BF16>(y, int64_t(m) * ldy + n0 + 16 * j + c, acc[t][j][i]);
+        }
+    return;
+  }
+  // fixed-order reduction over the K slices: element e = ((t NT + j) 4 + i) * 64 + lane
+  float* mine = red + wave * (T * 256);
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) mine[((t * NT + j) * 4 + i) * 64 + lane] = acc[t][j][i];
+  __syncthreads();
+  for (int e = threadIdx.x; e < T * 256; e += blockDim.x) {
+    float sum = red[e];
+    for (int s = 1; s < slices; ++s) sum += red[s * (T * 256) + e];
+    const int el = e & 63, ri = e >> 6;
+    const int tj = ri >> 2, t = tj / NT, j = tj - t * NT;
+    const int m = 16 * t + 4 * (el >> 4) + (ri & 3);
+    if (m < M) store_y<BF16>(y, int64_t(m) * ldy + n0 + 16 * j + (el & 15), sum);
+  }
+}
+
+template <int MT, int NT>
+void launch(bool bf16, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Mxfp4Layout& L, int64_t elem_off,
+            const uint16_t* x, int M, int K, void* y, int64_t ldy) {
+  if (bf16) mxfp4_linear_kernel<MT, NT, true><<<grid, block, lds, s>>>(L, elem_off, x, M, K, y, ldy);
+  else mxfp4_linear_kernel<MT, NT, false><<<grid, block, lds, s>>>(L, elem_off, x, M, K, y, ldy);
+}
+
+// Row tiles per wave and the most K slices for `mt` tiles along M: the
+// accumulators, the x fragments and two steps of weights must fit the
+// registers of a workgroup of that many waves, its partial sums 64 KiB of LDS.
+int max_slices(int mt, int nt) { return std::min(mt * nt <= 2 ? 16 : 8, 64 / (mt * nt)); }
+
+// Measured on MI355X over the llama3-70b projections (scripts/mxfp4_linear_bench.py,
+// profiles/mxfp4_linear/): many thin waves beat few wide ones until x traffic
+// counts, so a wave takes 2 row tiles from 256 tiles on and 4 (up to 32 rows of
+// x) from 1024 on ...
+int row_tiles(int mt, int64_t tiles) {
+  if (mt <= 2 && tiles >= 1024 && tiles % 4 == 0) return 4;
+  if (tiles >= 256 && tiles % 2 == 0) return 2;
+  return 1;
+}
+
+// ... and K is split until the grid has about 4096 waves for up to 8 rows of
+// x, 2048 up to 32 and 1024 beyond, with at least one step of 128 per slice.
+int auto_slices(int m, int mt, int nt, int64_t wgs, int64_t nsteps) {
+  const int64_t target = m <= 8 ? 4096 : mt <= 2 ? 2048 : 1024;
+  int s = 1;
+  while (2 * s <= max_slices(mt, nt) && wgs * s < target && 2 * s <= nsteps) s *= 2;
+  return s;
+}
+
+}  // namespace
+
+int mxfp4_linear_slices(int64_t M, int64_t N, int64_t K) {
+  const int mt = int(std::min<int64_t>(4, (M + 15) / 16));
+  const int nt = row_tiles(mt, N / 16);
+  return auto_slices(int(std::min<int64_t>(M, 64)), mt, nt, N / 16 / nt, K / 128);
+}
+
+hipError_t mxfp4_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, const uint16_t* x,
+                        int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
+                        int row_tiles_per_wave, hipStream_t s) {
+  if (src_chunk <= 0 || src_chunk % 1024 || src_bytes <= 0 || src_bytes % 64) return hipErrorInvalidValue;
+  if (M < 1 || N < 16 || N % 16 || K < 32 || K % 32 || K > 0x7FFFFF80 || N > 0x7FFFFFF0 || ldy < N)
+    return hipErrorInvalidValue;
+  if (elem_off < 0 || elem_off % 32 || N > (src_bytes / 2 - elem_off) / K) return hipErrorInvalidValue;
+  if ((reinterpret_cast<uintptr_t>(packed) & 15) || (reinterpret_cast<uintptr_t>(x) & 15) ||
+      (reinterpret_cast<uintptr_t>(y) & (y_bf16 ? 1 : 3)))
+    return hipErrorInvalidValue;
+  if (src_chunk / 64 > 0x7FFFFFFF) return hipErrorInvalidValue;
+  if (split_k < 0 || split_k > 16) return hipErrorInvalidValue;
+  const int rt = row_tiles_per_wave;
+  if ((rt != 0 && rt != 1 && rt != 2 && rt != 4) || (rt && N / 16 % rt)) return hipErrorInvalidValue;
+  Mxfp4Layout L;
+  L.packed = static_cast<const uint8_t*>(packed);
+  L.pchunk = src_chunk / 4 + src_chunk / 64;
+  L.full = src_bytes / src_chunk;
+  L.cblk = int(src_chunk / 64);
+  L.tblk = int(src_bytes % src_chunk / 64);
+  const size_t ysz = y_bf16 ? 2 : 4;
+  for (int64_t m0 = 0; m0 < M; m0 += 64) {
+    const int m = int(std::min<int64_t>(64, M - m0));
+    const int mt = (m + 15) / 16;
+    const int nt = rt ? std::min(rt, mt <= 2 ? 4 : 2) : row_tiles(mt, N / 16);
+    const int64_t wgs = N / 16 / nt;
+    const int slices = std::min(split_k ? split_k : auto_slices(m, mt, nt, wgs, K / 128), max_slices(mt, nt));
+    const dim3 grid{unsigned(wgs)}, block{unsigned(64 * slices)};
+    const size_t lds = slices > 1 ? size_t(slices) * mt * nt * 256 * sizeof(float) : 0;
+    const uint16_t* xp = x + m0 * K;
+    void* yp = static_cast<uint8_t*>(y) + size_t(m0) * size_t(ldy) * ysz;
+#define DISSEM_LINEAR_CASE(MT_, NT_) \
+  case MT_ * 8 + NT_: launch<MT_, NT_>(y_bf16, grid, block, lds, s, L, elem_off, xp, m, int(K), yp, ldy); break
+    switch (mt * 8 + nt) {
+      DISSEM_LINEAR_CASE(1, 1);
+      DISSEM_LINEAR_CASE(1, 2);
+      DISSEM_LINEAR_CASE(1, 4);
+      DISSEM_LINEAR_CASE(2, 1);
+      DISSEM_LINEAR_CASE(2, 2);
+      DISSEM_LINEAR_CASE(2, 4);
+      DISSEM_LINEAR_CASE(3, 1);
+      DISSEM_LINEAR_CASE(3, 2);
+      DISSEM_LINEAR_CASE(4, 1);
+      DISSEM_LINEAR_CASE(4, 2);
+      default: return hipErrorInvalidValue;
+    }
+#undef DISSEM_LINEAR_CASE
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace kern
+}  // namespace dissem

@@ -229,6 +229,41 @@ static void mxfp4_roundtrip() {
   }
 }
 
+// unpack_range_host against slices of the whole-layer unpack: chunks of 1024 B
+// and a layer with a 3-block tail chunk, ranges that start and end off the
+// block grid, cross chunks, end in the tail chunk and cover a NaN block; a
+// range that leaves the layer throws.
+static void mxfp4_range() {
+  std::vector<uint16_t> x(512 * 5 + 96);
+  std::mt19937 rng(11);
+  for (auto& v : x) v = uint16_t((rng() % 0x7F00) | ((rng() & 1) << 15));  // finite values
+  x[512 + 40] = 0x7FC1;  // a NaN block in chunk 1
+  const int64_t src = int64_t(x.size()) * 2, chunk = 1024;
+  std::vector<uint8_t> packed(size_t(mxfp4::packed_size(src, chunk)));
+  std::vector<uint16_t> whole(x.size());
+  mxfp4::pack_layer_host(reinterpret_cast<const uint8_t*>(x.data()), src, chunk, packed.data());
+  mxfp4::unpack_layer_host(packed.data(), src, chunk, reinterpret_cast<uint8_t*>(whole.data()));
+  const int64_t total = int64_t(x.size());
+  const int64_t ranges[][2] = {{0, total}, {0, 0}, {32 * 7, 96 * 4}, {500, 100}, {512 + 32, 32}, {7, 1},
+                               {512 * 4 + 480, 128}, {total - 33, 33}, {total, 0}};
+  for (const auto& r : ranges) {
+    std::vector<uint16_t> got(size_t(r[1]) + 1, 0xA5A5);
+    mxfp4::unpack_range_host(packed.data(), src, chunk, r[0], r[1], got.data());
+    EXPECT(got.back() == 0xA5A5);
+    EXPECT(std::equal(got.begin(), got.end() - 1, whole.begin() + r[0]));
+  }
+  int thrown = 0;
+  for (const auto& r : {std::pair<int64_t, int64_t>{total - 31, 32}, {-1, 4}, {total + 1, 0}, {0, -1}}) {
+    uint16_t sink[32];
+    try {
+      mxfp4::unpack_range_host(packed.data(), src, chunk, r.first, r.second, sink);
+    } catch (const std::runtime_error&) {
+      ++thrown;
+    }
+  }
+  EXPECT(thrown == 4);
+}
+
 int main(int argc, char** argv) {
   log::set_level(log::Error);
   // optional: run one case only (0-3 ring modes, 4-6 planned modes 1-3, 7 corruption, 8-9 rank death,
@@ -249,6 +284,7 @@ int main(int argc, char** argv) {
   for (int mode = 1; mode <= 3; ++mode)
     if (on(10 + mode)) planned_sim(mode, 0, -1, mode == 2, true);
   if (on(14)) mxfp4_roundtrip();
+  if (on(15)) mxfp4_range();
   if (failures) {
     fprintf(stderr, "%d failures\n", failures);
     return 1;

@@ -325,7 +325,8 @@ def _weights_source(spec):
 def _check_weights(rt, spec, layers, my_id: int) -> None:
     """Serving smoke: each assigned layer as named parameters (zero-copy views in
     HBM on the rccl engine), one forward pass, compared with the same pass on the
-    seeded weights."""
+    seeded weights. With --pack mxfp4 --store packed the pass runs from the packed
+    slot (ops.mxfp4_linear), with no bf16 copy of the weights."""
     import torch
 
     from .models.weights import decoder_forward, random_layer
@@ -333,7 +334,7 @@ def _check_weights(rt, spec, layers, my_id: int) -> None:
     x = torch.randn(1, 8, spec.hidden, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
     worst = 0.0
     for l in sorted(layers):
-        p = rt.layer_params(l, spec)
+        p = rt.layer_params(l, spec, packed=rt.pack == "mxfp4" and rt.store == "packed")
         dev = next(iter(p.values())).device
         y = decoder_forward(x.to(dev), p, spec).float().cpu()
         y0 = decoder_forward(x, random_layer(spec, 1000 + l), spec).float()

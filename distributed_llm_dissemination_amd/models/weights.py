@@ -14,6 +14,11 @@ chunk grid both fit) - and converts between the two:
     params = rt.layer_params(l, spec)             # named bf16 views of the layer in HBM (zero-copy)
     y = decoder_forward(x, params, spec)          # use them
 
+With ``--pack mxfp4 --store packed`` the layer stays packed in HBM and is used
+as it lies: ``rt.layer_params(l, spec, packed=True)`` gives a ``PackedParam`` per
+name (views of the packed slot, no bf16 image anywhere) and ``decoder_forward``
+runs every linear through ``ops.mxfp4_linear``.
+
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
 on received weights against the originals.
@@ -22,7 +27,7 @@ on received weights against the originals.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -126,6 +131,68 @@ def unflatten(blob: torch.Tensor, spec: DecoderSpec) -> Dict[str, torch.Tensor]:
     return out
 
 
+@dataclass(frozen=True)
+class PackedParam:
+    """One parameter of a layer that is held MXFP4-packed (core/mxfp4.h): elements
+    [elem_offset, elem_offset + numel) of the layer of `src_bytes` bf16 bytes whose
+    packed image, in chunks of `chunk_bytes`, is `packed`. A view: nothing is copied."""
+    packed: torch.Tensor
+    src_bytes: int
+    chunk_bytes: int
+    elem_offset: int
+    shape: Tuple[int, ...]
+
+    @property
+    def device(self) -> torch.device:
+        return self.packed.device
+
+    def dequantize(self) -> torch.Tensor:
+        """The parameter as a bf16 tensor on the packed tensor's device."""
+        from ..ops import mxfp4_unpack_range
+
+        return mxfp4_unpack_range(self.packed, self.src_bytes, self.chunk_bytes, self.elem_offset,
+                                  _numel(self.shape)).view(self.shape)
+
+
+Param = Union[torch.Tensor, PackedParam]
+
+
+def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int) -> Dict[str, PackedParam]:
+    """Named parameters of an MXFP4-packed layer blob (a uint8 tensor on any device,
+    the image of layer_nbytes(spec) source bytes in chunks of `chunk_bytes`; no copy)."""
+    from ..ops import mxfp4_packed_size
+
+    if packed.dtype != torch.uint8:
+        raise ValueError("packed must be uint8")
+    packed = packed.view(-1)
+    src = layer_nbytes(spec)
+    if chunk_bytes <= 0 or chunk_bytes % 1024:
+        raise ValueError("chunk_bytes must be a positive multiple of 1024")
+    need = mxfp4_packed_size(src, chunk_bytes)
+    if packed.numel() < need:
+        raise ValueError(f"packed holds {packed.numel()} B, the layer's packed image needs {need}")
+    out = {}
+    off = 0
+    for name, shape in layer_params(spec):
+        out[name] = PackedParam(packed, src, chunk_bytes, off, tuple(shape))
+        off += _numel(shape)
+    return out
+
+
+def _linear(x: torch.Tensor, w: Param) -> torch.Tensor:
+    """x @ w.T: from the packed bytes for a PackedParam, F.linear for a tensor."""
+    if isinstance(w, PackedParam):
+        from ..ops import mxfp4_linear
+
+        return mxfp4_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
+                            elem_offset=w.elem_offset, out_dtype=x.dtype)
+    return F.linear(x, w)
+
+
+def _dense(w: Param) -> torch.Tensor:
+    return w.dequantize() if isinstance(w, PackedParam) else w
+
+
 def _rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     xf = x.float()
     return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps) * w.float()).to(x.dtype)
@@ -142,18 +209,20 @@ def _rope(x: torch.Tensor, theta: float) -> torch.Tensor:
     return (x.float() * cos + torch.cat([-x2, x1], -1) * sin).to(x.dtype)
 
 
-def decoder_forward(x: torch.Tensor, p: Dict[str, torch.Tensor], spec: DecoderSpec) -> torch.Tensor:
-    """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache)."""
+def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec) -> torch.Tensor:
+    """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
+    Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
+    packed bytes (ops.mxfp4_linear), a packed norm weight is dequantized once."""
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
-    h = _rms_norm(x, p["input_layernorm"], spec.eps)
-    q = F.linear(h, p["q_proj"]).view(b, s, nh, hd).transpose(1, 2)
-    k = F.linear(h, p["k_proj"]).view(b, s, nkv, hd).transpose(1, 2)
-    v = F.linear(h, p["v_proj"]).view(b, s, nkv, hd).transpose(1, 2)
+    h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
+    q = _linear(h, p["q_proj"]).view(b, s, nh, hd).transpose(1, 2)
+    k = _linear(h, p["k_proj"]).view(b, s, nkv, hd).transpose(1, 2)
+    v = _linear(h, p["v_proj"]).view(b, s, nkv, hd).transpose(1, 2)
     q, k = _rope(q, spec.rope_theta), _rope(k, spec.rope_theta)
     k = k.repeat_interleave(nh // nkv, dim=1)
     v = v.repeat_interleave(nh // nkv, dim=1)
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-    x = x + F.linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"])
-    h = _rms_norm(x, p["post_attention_layernorm"], spec.eps)
-    return x + F.linear(F.silu(F.linear(h, p["gate_proj"])) * F.linear(h, p["up_proj"]), p["down_proj"])
+    x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"])
+    h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
+    return x + _linear(F.silu(_linear(h, p["gate_proj"])) * _linear(h, p["up_proj"]), p["down_proj"])

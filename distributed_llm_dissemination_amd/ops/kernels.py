@@ -1,7 +1,8 @@
 """PyTorch-facing wrappers of the gfx950 kernels (csrc/kernels/*.hip).
 
-Every op takes and returns CUDA (HIP) tensors and runs on the caller's current
-stream, so it composes with PyTorch work without extra synchronization. Shapes,
+Every op takes and returns CUDA (HIP) tensors (the two consumers of a packed
+layer, mxfp4_unpack_range and mxfp4_linear, also take CPU tensors and then use
+the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
 dtypes, alignment and sizes are checked on the host before any launch (a kernel
 must never be handed a buffer smaller than its grid assumes).
 
@@ -12,6 +13,10 @@ must never be handed a buffer smaller than its grid assumes).
     y = ops.fp8_unpack(q, s)                  # bf16 again
     q4, s4 = ops.mxfp4_pack(x)                # MXFP4: e2m1 pairs + one E8M0 scale per 32 values
     crc = ops.crc32c(x.view(torch.uint8), 64 << 20)   # CRC32C per 64 MiB chunk
+    w = x.view(4096, 4096)                              # a bf16 [out, in] weight ...
+    p = ops.mxfp4_pack_layer(x, 64 << 20)               # ... as an MXFP4-packed layer (17/64 of the bytes)
+    h = torch.randn(8, 4096, dtype=torch.bfloat16, device="cuda")
+    y = ops.mxfp4_linear(h, p, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20)   # h @ w.T from the packed bytes
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
 per-chunk CRC verification of every landed chunk); here they are usable on
@@ -20,7 +25,7 @@ their own, e.g. to check or unpack a layer a rank received.
 
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -42,6 +47,8 @@ __all__ = [
     "mxfp4_verify_unpack",
     "mxfp4_verify_unpack_chunks",
     "mxfp4_packed_size",
+    "mxfp4_unpack_range",
+    "mxfp4_linear",
 ]
 
 _FP8_BLOCKS = (32, 64, 128, 256, 512)
@@ -307,3 +314,117 @@ def mxfp4_verify_unpack_chunks(chunks: List[Tuple[torch.Tensor, int]]) -> Tuple[
     ws = torch.zeros(_core.crc32c_batch_workspace_bytes(), dtype=torch.uint8, device=dev)
     _core.mxfp4_verify_unpack_batch_async(items, crcs.data_ptr(), ws.data_ptr(), _stream())
     return outs, crcs
+
+
+# ---- consumers of a packed layer in place: a parameter is the elements
+# [elem_offset, elem_offset + numel) of the layer (core/mxfp4.h unpack_range_host)
+
+def _check_packed_layer(packed: torch.Tensor, src_bytes: int, chunk_bytes: int) -> int:
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous 1-D uint8 tensor")
+    if chunk_bytes <= 0 or chunk_bytes % 1024 or src_bytes <= 0 or src_bytes % (2 * _MX_BLOCK):
+        raise ValueError("chunk_bytes must be a positive multiple of 1024 and src_bytes a positive multiple of 64")
+    need = mxfp4_packed_size(src_bytes, chunk_bytes)
+    if packed.numel() < need:
+        raise ValueError(f"packed holds {packed.numel()} bytes, the layout needs {need}")
+    if packed.is_cuda and packed.data_ptr() % 16:
+        raise ValueError("packed must be 16-byte aligned")
+    return need
+
+
+def _check_range(src_bytes: int, elem_offset: int, n: int) -> None:
+    if elem_offset < 0 or n < 0 or elem_offset % _MX_BLOCK or n % _MX_BLOCK:
+        raise ValueError(f"elem_offset and the element count must be non-negative multiples of {_MX_BLOCK}")
+    if elem_offset + n > src_bytes // 2:
+        raise ValueError(f"elements [{elem_offset}, {elem_offset + n}) lie outside a layer of {src_bytes // 2}")
+
+
+def mxfp4_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, elem_offset: int, n: int) -> torch.Tensor:
+    """Elements [elem_offset, elem_offset + n) of an MXFP4-packed layer (the chunked
+    layout of `mxfp4_pack_layer`) as bf16 [n], on `packed`'s device. Offset and
+    count are multiples of 32. GPU: the unpack kernel once per source chunk the
+    range touches, on the current stream; CPU: the host reference."""
+    _check_packed_layer(packed, src_bytes, chunk_bytes)
+    _check_range(src_bytes, elem_offset, n)
+    out = torch.empty(n, dtype=torch.bfloat16, device=packed.device)
+    if n == 0:
+        return out
+    if not packed.is_cuda:
+        _core.mxfp4_unpack_range_host(packed.data_ptr(), packed.numel(), src_bytes, chunk_bytes, elem_offset, n,
+                                      out.data_ptr())
+        return out
+    total, ce, pchunk = src_bytes // 2, chunk_bytes // 2, chunk_bytes // 4 + chunk_bytes // 64
+    e, end, stream = elem_offset, elem_offset + n, _stream()
+    while e < end:
+        c, r = divmod(e, ce)
+        nc = min(ce, total - c * ce)
+        take = min(end - e, nc - r)
+        base = packed.data_ptr() + c * pchunk
+        # r and e - elem_offset are multiples of 32: q 16-B, the output 64-B aligned
+        _core.mxfp4_unpack(base + r // 2, base + nc // 2 + r // _MX_BLOCK, take, out.data_ptr() + 2 * (e - elem_offset),
+                           stream)
+        e += take
+    return out
+
+
+def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
+                 chunk_bytes: int, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
+    weight stored as elements [elem_offset, ...) of the MXFP4-packed layer `packed`
+    (`src_bytes` of bf16 in chunks of `chunk_bytes`, the layout of `mxfp4_pack_layer`).
+
+    GPU: one kernel on the current stream reads the codes and scales where they
+    lie, dequantizes in registers and accumulates in f32 on the bf16 MFMA; no bf16
+    copy of the weight is made. The result is deterministic (`split_k`, 0 = chosen
+    from the shape, is the number of K slices reduced in a fixed order; `row_tiles`,
+    0 = chosen from the shape, the 16-row tiles of W a wave feeds from one x fragment).
+    CPU: the host reference dequantizes the range, then ``F.linear`` - in f32 for an
+    f32 result, in bf16 (what a plain bf16 weight gets) for a bf16 one.
+    in_features and elem_offset are multiples of 32, out_features of 16.
+    `out` (GPU only): a [rows, out_features] f32 or bf16 tensor to write, unit
+    stride along its rows and any row stride; its dtype replaces `out_dtype`."""
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"x must be {torch.bfloat16}, got {x.dtype}")
+    n, k = int(out_features), int(in_features)
+    if n <= 0 or n % 16 or k <= 0 or k % _MX_BLOCK:
+        raise ValueError("out_features must be a positive multiple of 16 and in_features of 32")
+    if x.dim() < 1 or x.shape[-1] != k or x.numel() == 0:
+        raise ValueError(f"x must be [..., {k}] with at least one row, got {tuple(x.shape)}")
+    if x.device != packed.device:
+        raise ValueError("x and packed must be on the same device")
+    if not 0 <= split_k <= 16:
+        raise ValueError("split_k must be in 0..16")
+    if row_tiles not in (0, 1, 2, 4) or (row_tiles and n // 16 % row_tiles):
+        raise ValueError("row_tiles must be 0, 1, 2 or 4 and divide out_features / 16")
+    _check_packed_layer(packed, src_bytes, chunk_bytes)
+    _check_range(src_bytes, elem_offset, n * k)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, k)
+    if not x.is_cuda:
+        if out is not None:
+            raise ValueError("out is for GPU tensors")
+        w = mxfp4_unpack_range(packed, src_bytes, chunk_bytes, elem_offset, n * k).view(n, k)
+        if out_dtype == torch.float32:
+            y = torch.nn.functional.linear(x2.float(), w.float())
+        else:
+            y = torch.nn.functional.linear(x2, w)
+        return y.view(*lead, n)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() % 16:
+        x2 = x2.clone()
+    m = x2.shape[0]
+    if out is None:
+        y = torch.empty(m, n, dtype=out_dtype, device=x.device)
+    else:
+        y = out
+        if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
+            raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    _core.mxfp4_linear(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k, y.data_ptr(),
+                       y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
+    return y if out is not None else y.view(*lead, n)

@@ -1198,12 +1198,20 @@ class Runtime:
         dev = torch.device("cuda", self.device)
         return torch.as_tensor(_DeviceBytes(self, ptr, n), device=dev)
 
-    def layer_params(self, layer: int, spec):
+    def layer_params(self, layer: int, spec, packed: bool = False):
         """Named bf16 parameter views of a layer that holds a models/weights.py
         blob: zero-copy in HBM on the rccl engine (the dequantized image with
-        --pack fp8 / mxfp4 and --store bf16), CPU copies otherwise."""
-        from ..models.weights import unflatten
+        --pack fp8 / mxfp4 and --store bf16), CPU copies otherwise.
 
+        ``packed=True`` (--pack mxfp4 --store packed only): a PackedParam per name
+        over layer_tensor(layer) - the packed slot itself on the rccl engine, with
+        no bf16 image - for decoder_forward / ops.mxfp4_linear to use in place."""
+        from ..models.weights import unflatten, unflatten_packed
+
+        if packed:
+            if self.pack != "mxfp4" or self.store != "packed":
+                raise ValueError("packed parameters need --pack mxfp4 --store packed")
+            return unflatten_packed(self.layer_tensor(layer), spec, self.chunk_bytes)
         if self.pack != "none" and self.store != "bf16":
             import torch
 
