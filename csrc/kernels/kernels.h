@@ -118,5 +118,21 @@ hipError_t mxfp4_linear(const void* packed, int64_t src_bytes, int64_t src_chunk
                         int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
                         int row_tiles_per_wave, hipStream_t s);
 
+// ---- mxfp4_swiglu.hip: y[m][n] = silu(g[m][n]) * u[m][n] with g = x * Wg^T and
+// u = x * Wu^T, Wg and Wu the [N, K] parameters at elements `gate_off` and
+// `up_off` of one packed layer (independent multiples of 32, in any order,
+// possibly equal). Arguments, checks and accumulation are mxfp4_linear's, for
+// both parameters; g and u never leave the accumulators, and with equal K
+// slices they are bit for bit mxfp4_linear's f32 results. The epilogue is
+// (g / (1 + expf(-g))) * u in f32, stored as f32 or as bf16 (nearest even).
+// `split_k`: 0 = chosen (mxfp4_swiglu_slices), else 1..16, clamped to what the
+// registers and 64 KiB of LDS allow. `row_tiles_per_wave` counts pairs of a
+// gate and an up tile: 0 = chosen, 1 or 2 (a divisor of N / 16; 1 beyond 32
+// rows of x). Stream-ordered, no allocation, no workspace, no atomics.
+int mxfp4_swiglu_slices(int64_t M, int64_t N, int64_t K);
+hipError_t mxfp4_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
+                        const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
+                        int split_k, int row_tiles_per_wave, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

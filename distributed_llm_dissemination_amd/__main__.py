@@ -326,7 +326,8 @@ def _check_weights(rt, spec, layers, my_id: int) -> None:
     """Serving smoke: each assigned layer as named parameters (zero-copy views in
     HBM on the rccl engine), one forward pass, compared with the same pass on the
     seeded weights. With --pack mxfp4 --store packed the pass runs from the packed
-    slot (ops.mxfp4_linear), with no bf16 copy of the weights."""
+    slot (ops.mxfp4_linear for q/k/v, o and down, ops.mxfp4_swiglu for the gated
+    front half of the MLP), with no bf16 copy of the weights."""
     import torch
 
     from .models.weights import decoder_forward, random_layer

@@ -17,7 +17,11 @@ chunk grid both fit) - and converts between the two:
 With ``--pack mxfp4 --store packed`` the layer stays packed in HBM and is used
 as it lies: ``rt.layer_params(l, spec, packed=True)`` gives a ``PackedParam`` per
 name (views of the packed slot, no bf16 image anywhere) and ``decoder_forward``
-runs every linear through ``ops.mxfp4_linear``.
+runs the layer from the packed bytes in four weight launches: q, k and v, which
+lie one behind the other in the blob, as one ``ops.mxfp4_linear`` of h + 2 kv rows
+(on the GPU), ``o_proj``, the gate and up projections with ``silu(g) * u`` as one
+``ops.mxfp4_swiglu``, and ``down_proj``. ``fuse=False`` runs one ``ops.mxfp4_linear``
+per projection instead.
 
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
@@ -209,20 +213,61 @@ def _rope(x: torch.Tensor, theta: float) -> torch.Tensor:
     return (x.float() * cos + torch.cat([-x2, x1], -1) * sin).to(x.dtype)
 
 
-def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec) -> torch.Tensor:
+def _same_layer(*ws: Param) -> bool:
+    """All PackedParams over the same packed bytes with one layout."""
+    if not all(isinstance(w, PackedParam) for w in ws):
+        return False
+    p0 = ws[0].packed
+    return all(w.packed.device == p0.device and w.packed.data_ptr() == p0.data_ptr() and w.packed.numel() == p0.numel()
+               and w.src_bytes == ws[0].src_bytes and w.chunk_bytes == ws[0].chunk_bytes for w in ws[1:])
+
+
+def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
+    """q, k and v of h. On the GPU, three PackedParams of one layer that lie one behind
+    the other with equal in_features are one [h + 2 kv, h] weight and take one launch;
+    the result is split by views. On the CPU (and for anything else) one call each."""
+    wq, wk, wv = p["q_proj"], p["k_proj"], p["v_proj"]
+    if (fuse and h.is_cuda and _same_layer(wq, wk, wv) and wq.shape[1] == wk.shape[1] == wv.shape[1]
+            and wk.elem_offset == wq.elem_offset + _numel(wq.shape)
+            and wv.elem_offset == wk.elem_offset + _numel(wk.shape)):
+        from ..ops import mxfp4_linear
+
+        nq, nk, nv = wq.shape[0], wk.shape[0], wv.shape[0]
+        y = mxfp4_linear(h, wq.packed, nq + nk + nv, wq.shape[1], src_bytes=wq.src_bytes, chunk_bytes=wq.chunk_bytes,
+                         elem_offset=wq.elem_offset, out_dtype=h.dtype)
+        return y[..., :nq], y[..., nq:nq + nk], y[..., nq + nk:]
+    return _linear(h, wq), _linear(h, wk), _linear(h, wv)
+
+
+def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool) -> torch.Tensor:
+    """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two PackedParams of one
+    layer with equal shapes (on the CPU the very ops of the other route)."""
+    if fuse and _same_layer(wg, wu) and wg.shape == wu.shape:
+        from ..ops import mxfp4_swiglu
+
+        return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes,
+                            gate_offset=wg.elem_offset, up_offset=wu.elem_offset, out_dtype=h.dtype)
+    return F.silu(_linear(h, wg)) * _linear(h, wu)
+
+
+def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
-    packed bytes (ops.mxfp4_linear), a packed norm weight is dequantized once."""
+    packed bytes (ops.mxfp4_linear), a packed norm weight is dequantized once. With
+    `fuse`, packed gate and up projections run as one ops.mxfp4_swiglu and, on the GPU,
+    packed q, k and v as one ops.mxfp4_linear; parameters that do not allow it (a mix
+    of tensors and PackedParams, other layouts) fall back per projection."""
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
-    q = _linear(h, p["q_proj"]).view(b, s, nh, hd).transpose(1, 2)
-    k = _linear(h, p["k_proj"]).view(b, s, nkv, hd).transpose(1, 2)
-    v = _linear(h, p["v_proj"]).view(b, s, nkv, hd).transpose(1, 2)
+    q, k, v = _qkv(h, p, fuse)
+    q = q.view(b, s, nh, hd).transpose(1, 2)
+    k = k.view(b, s, nkv, hd).transpose(1, 2)
+    v = v.view(b, s, nkv, hd).transpose(1, 2)
     q, k = _rope(q, spec.rope_theta), _rope(k, spec.rope_theta)
     k = k.repeat_interleave(nh // nkv, dim=1)
     v = v.repeat_interleave(nh // nkv, dim=1)
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
     x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"])
     h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-    return x + _linear(F.silu(_linear(h, p["gate_proj"])) * _linear(h, p["up_proj"]), p["down_proj"])
+    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse), p["down_proj"])

@@ -1,8 +1,8 @@
 """PyTorch-facing wrappers of the gfx950 kernels (csrc/kernels/*.hip).
 
-Every op takes and returns CUDA (HIP) tensors (the two consumers of a packed
-layer, mxfp4_unpack_range and mxfp4_linear, also take CPU tensors and then use
-the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
+Every op takes and returns CUDA (HIP) tensors (the consumers of a packed
+layer, mxfp4_unpack_range, mxfp4_linear and mxfp4_swiglu, also take CPU tensors
+and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
 dtypes, alignment and sizes are checked on the host before any launch (a kernel
 must never be handed a buffer smaller than its grid assumes).
 
@@ -17,6 +17,8 @@ must never be handed a buffer smaller than its grid assumes).
     p = ops.mxfp4_pack_layer(x, 64 << 20)               # ... as an MXFP4-packed layer (17/64 of the bytes)
     h = torch.randn(8, 4096, dtype=torch.bfloat16, device="cuda")
     y = ops.mxfp4_linear(h, p, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20)   # h @ w.T from the packed bytes
+    z = ops.mxfp4_swiglu(h, p, 2048, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20,   # silu(h @ wg.T) * (h @ wu.T),
+                         gate_offset=0, up_offset=2048 * 4096)                              # wg, wu = w[:2048], w[2048:]
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
 per-chunk CRC verification of every landed chunk); here they are usable on
@@ -49,6 +51,7 @@ __all__ = [
     "mxfp4_packed_size",
     "mxfp4_unpack_range",
     "mxfp4_linear",
+    "mxfp4_swiglu",
 ]
 
 _FP8_BLOCKS = (32, 64, 128, 256, 512)
@@ -427,4 +430,69 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
     _core.mxfp4_linear(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k, y.data_ptr(),
                        y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
+    return y if out is not None else y.view(*lead, n)
+
+
+def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
+                 chunk_bytes: int, gate_offset: int, up_offset: int, out_dtype: torch.dtype = torch.bfloat16,
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``silu(x @ Wg.T) * (x @ Wu.T)``, the front half of a gated MLP, for a bf16 `x`
+    [..., in_features] and two [out_features, in_features] weights stored as elements
+    [gate_offset, ...) and [up_offset, ...) of the MXFP4-packed layer `packed` (as in
+    `mxfp4_linear`; the offsets are independent multiples of 32, in any order).
+
+    GPU: one kernel on the current stream reads x once and both weights where they
+    lie; the two products are `mxfp4_linear`'s sums (with equal `split_k` bit for
+    bit its f32 results) and stay in the MFMA accumulators, ``(g / (1 + expf(-g))) * u``
+    is evaluated in f32 and only the result is written, rounded once. `split_k`
+    as in `mxfp4_linear`; `row_tiles` (0 = chosen from the shape, 1 or 2): the pairs
+    of a gate and an up tile a wave feeds from one x fragment.
+    CPU: the host reference dequantizes both ranges, then
+    ``F.silu(F.linear(x, wg)) * F.linear(x, wu)`` - in f32 for an f32 result, in bf16
+    (what plain bf16 weights get, op for op) for a bf16 one.
+    `out` (GPU only) as in `mxfp4_linear`."""
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"x must be {torch.bfloat16}, got {x.dtype}")
+    n, k = int(out_features), int(in_features)
+    if n <= 0 or n % 16 or k <= 0 or k % _MX_BLOCK:
+        raise ValueError("out_features must be a positive multiple of 16 and in_features of 32")
+    if x.dim() < 1 or x.shape[-1] != k or x.numel() == 0:
+        raise ValueError(f"x must be [..., {k}] with at least one row, got {tuple(x.shape)}")
+    if x.device != packed.device:
+        raise ValueError("x and packed must be on the same device")
+    if not 0 <= split_k <= 16:
+        raise ValueError("split_k must be in 0..16")
+    if row_tiles not in (0, 1, 2) or (row_tiles and n // 16 % row_tiles):
+        raise ValueError("row_tiles must be 0, 1 or 2 and divide out_features / 16")
+    _check_packed_layer(packed, src_bytes, chunk_bytes)
+    _check_range(src_bytes, gate_offset, n * k)
+    _check_range(src_bytes, up_offset, n * k)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, k)
+    if not x.is_cuda:
+        if out is not None:
+            raise ValueError("out is for GPU tensors")
+        wg = mxfp4_unpack_range(packed, src_bytes, chunk_bytes, gate_offset, n * k).view(n, k)
+        wu = mxfp4_unpack_range(packed, src_bytes, chunk_bytes, up_offset, n * k).view(n, k)
+        if out_dtype == torch.float32:
+            x2, wg, wu = x2.float(), wg.float(), wu.float()
+        y = torch.nn.functional.silu(torch.nn.functional.linear(x2, wg)) * torch.nn.functional.linear(x2, wu)
+        return y.view(*lead, n)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() % 16:
+        x2 = x2.clone()
+    m = x2.shape[0]
+    if out is None:
+        y = torch.empty(m, n, dtype=out_dtype, device=x.device)
+    else:
+        y = out
+        if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
+            raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    _core.mxfp4_swiglu(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n, k,
+                       y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)

@@ -1205,7 +1205,9 @@ class Runtime:
 
         ``packed=True`` (--pack mxfp4 --store packed only): a PackedParam per name
         over layer_tensor(layer) - the packed slot itself on the rccl engine, with
-        no bf16 image - for decoder_forward / ops.mxfp4_linear to use in place."""
+        no bf16 image - for decoder_forward to use in place: ops.mxfp4_linear per
+        projection, q/k/v in one launch on the GPU, and gate and up with
+        silu(g) * u in one ops.mxfp4_swiglu."""
         from ..models.weights import unflatten, unflatten_packed
 
         if packed:
