@@ -546,6 +546,17 @@ PYBIND11_MODULE(_core, m) {
     }
     return py::bytes(out);
   }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block") = 128);
+  // elements [elem_off, elem_off + n) of a packed layer in host memory at `packed` -> n bf16 at `out`
+  m.def("fp8_unpack_range_host", [](uint64_t packed, int64_t packed_bytes, int64_t src_bytes, int64_t src_chunk,
+                                    int block, int64_t elem_off, int64_t n, uint64_t out) {
+    fp8::check(src_bytes, src_chunk, block);
+    if (packed_bytes < fp8::packed_size(src_bytes, src_chunk, block))
+      throw std::runtime_error("packed buffer is smaller than the layer's packed size");
+    py::gil_scoped_release nogil;
+    fp8::unpack_range_host(reinterpret_cast<const uint8_t*>(packed), src_bytes, src_chunk, block, elem_off, n,
+                           reinterpret_cast<uint16_t*>(out));
+  }, py::arg("packed"), py::arg("packed_bytes"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block"),
+     py::arg("elem_off"), py::arg("n"), py::arg("out"));
   // MXFP4 wire/storage format (core/mxfp4.h), host reference
   m.def("mxfp4_packed_size", &mxfp4::packed_size, py::arg("src_bytes"), py::arg("src_chunk"));
   m.def("mxfp4_source_size", &mxfp4::source_size, py::arg("packed"), py::arg("src_chunk"));

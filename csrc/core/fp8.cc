@@ -101,5 +101,30 @@ void unpack_layer_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chu
   }
 }
 
+void unpack_range_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
+                       int64_t n, uint16_t* out) {
+  check(src_bytes, src_chunk, block);
+  if (src_bytes <= 0 || src_chunk <= 0) throw std::runtime_error("fp8 layer and chunk sizes must be positive");
+  const int64_t total = src_bytes / 2, ce = src_chunk / 2;
+  if (elem_off < 0 || n < 0 || elem_off > total || n > total - elem_off)
+    throw std::runtime_error("fp8 element range lies outside the layer");
+  for (int64_t e = elem_off, end = elem_off + n; e < end;) {
+    const int64_t c = e / ce, r = e - c * ce;
+    const int64_t nc = std::min(ce, total - c * ce);  // elements of this chunk
+    const int64_t take = std::min(end - e, nc - r);
+    const uint8_t* q = packed + c * packed_chunk(src_chunk, block);
+    // one scale block (or the part of it in the range) per unpack_host call, with its scale copied
+    // out: `packed` may have any alignment
+    const int64_t b0 = r / block, b1 = (r + take + block - 1) / block;
+    for (int64_t b = b0; b < b1; ++b) {
+      float s;
+      memcpy(&s, q + nc + 4 * b, 4);
+      const int64_t lo = std::max(r, b * block), hi = std::min(r + take, (b + 1) * block);
+      unpack_host(q + lo, &s, hi - lo, out + (e - elem_off) + (lo - r), block);
+    }
+    e += take;
+  }
+}
+
 }  // namespace fp8
 }  // namespace dissem

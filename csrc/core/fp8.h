@@ -95,6 +95,15 @@ void unpack_host(const uint8_t* q, const float* scales, int64_t n, uint16_t* bf1
 // Whole layer: src_bytes of bf16 -> packed_size(...) bytes in the chunked layout.
 void pack_layer_host(const uint8_t* src, int64_t src_bytes, int64_t src_chunk, int block, uint8_t* dst);
 void unpack_layer_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chunk, int block, uint8_t* dst);
+// Elements [elem_off, elem_off + n) of the packed layer (any offset and length
+// inside it; throws otherwise): the one definition of where an element lives.
+// Element e is in chunk c = e / (src_chunk / 2); with r = e - c * (src_chunk / 2)
+// and n_c the elements of that chunk (the tail chunk is laid out on its own
+// length), its code is byte r of the packed chunk and its f32 scale is at byte
+// n_c + 4 * (r / block). What a consumer of the packed bytes in place
+// (kernels/fp8_linear.hip) reads; the values are unpack_host's.
+void unpack_range_host(const uint8_t* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
+                       int64_t n, uint16_t* out);
 
 }  // namespace fp8
 }  // namespace dissem

@@ -134,5 +134,20 @@ hipError_t mxfp4_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk
                         const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
                         int split_k, int row_tiles_per_wave, hipStream_t s);
 
+// ---- fp8_linear.hip: the same product with W read in place from an fp8-packed
+// layer (core/fp8.h: e4m3 codes and one power-of-two f32 scale per `block`
+// elements, per source chunk; fp8::unpack_range_host defines where an element
+// lies). The contract is mxfp4_linear's - x, y, ldy, M, N, K, elem_off (a
+// multiple of 32), f32 accumulation on v_mfma_f32_16x16x32_bf16, `split_k`,
+// `row_tiles_per_wave`, stream order, no allocation, no workspace, no atomics,
+// equal inputs give equal bits - and in addition: `block` is 32, 64, 128, 256
+// or 512; `src_chunk` is a multiple of 8 * block bytes (every packed chunk,
+// n + 4 n / block bytes, then starts 16-B aligned); `src_bytes` a multiple of
+// 2 * block; `packed` 16-B aligned. Anything else: hipErrorInvalidValue.
+int fp8_linear_slices(int64_t M, int64_t N, int64_t K);
+hipError_t fp8_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
+                      const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
+                      int split_k, int row_tiles_per_wave, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

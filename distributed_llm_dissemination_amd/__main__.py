@@ -327,7 +327,8 @@ def _check_weights(rt, spec, layers, my_id: int) -> None:
     HBM on the rccl engine), one forward pass, compared with the same pass on the
     seeded weights. With --pack mxfp4 --store packed the pass runs from the packed
     slot (ops.mxfp4_linear for q/k/v, o and down, ops.mxfp4_swiglu for the gated
-    front half of the MLP), with no bf16 copy of the weights."""
+    front half of the MLP), with no bf16 copy of the weights; with --pack fp8
+    --store packed likewise, through ops.fp8_linear."""
     import torch
 
     from .models.weights import decoder_forward, random_layer
@@ -335,7 +336,10 @@ def _check_weights(rt, spec, layers, my_id: int) -> None:
     x = torch.randn(1, 8, spec.hidden, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
     worst = 0.0
     for l in sorted(layers):
-        p = rt.layer_params(l, spec, packed=rt.pack == "mxfp4" and rt.store == "packed")
+        if rt.pack != "none" and rt.store == "packed":
+            p = rt.packed_layer_params(l, spec)
+        else:
+            p = rt.layer_params(l, spec)
         dev = next(iter(p.values())).device
         y = decoder_forward(x.to(dev), p, spec).float().cpu()
         y0 = decoder_forward(x, random_layer(spec, 1000 + l), spec).float()

@@ -23,6 +23,12 @@ lie one behind the other in the blob, as one ``ops.mxfp4_linear`` of h + 2 kv ro
 ``ops.mxfp4_swiglu``, and ``down_proj``. ``fuse=False`` runs one ``ops.mxfp4_linear``
 per projection instead.
 
+``--pack fp8 --store packed`` is served the same way: ``rt.packed_layer_params(l, spec)``
+(which serves both formats) gives ``PackedParam``s with ``fmt="fp8"`` and the session's
+scale block, and ``decoder_forward`` runs the layer from the e4m3 codes and block scales in
+five weight launches: q/k/v as one ``ops.fp8_linear``, ``o_proj``, gate, up (there is no fused
+fp8 SwiGLU; ``silu(g) * u`` is plain torch) and ``down_proj``.
+
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
 on received weights against the originals.
@@ -137,14 +143,17 @@ def unflatten(blob: torch.Tensor, spec: DecoderSpec) -> Dict[str, torch.Tensor]:
 
 @dataclass(frozen=True)
 class PackedParam:
-    """One parameter of a layer that is held MXFP4-packed (core/mxfp4.h): elements
-    [elem_offset, elem_offset + numel) of the layer of `src_bytes` bf16 bytes whose
-    packed image, in chunks of `chunk_bytes`, is `packed`. A view: nothing is copied."""
+    """One parameter of a layer that is held packed - `fmt` "mxfp4" (core/mxfp4.h) or
+    "fp8" (core/fp8.h, one scale per `block` elements): elements [elem_offset,
+    elem_offset + numel) of the layer of `src_bytes` bf16 bytes whose packed image, in
+    chunks of `chunk_bytes`, is `packed`. A view: nothing is copied."""
     packed: torch.Tensor
     src_bytes: int
     chunk_bytes: int
     elem_offset: int
     shape: Tuple[int, ...]
+    fmt: str = "mxfp4"
+    block: int = 32
 
     @property
     def device(self) -> torch.device:
@@ -152,8 +161,11 @@ class PackedParam:
 
     def dequantize(self) -> torch.Tensor:
         """The parameter as a bf16 tensor on the packed tensor's device."""
-        from ..ops import mxfp4_unpack_range
+        from ..ops import fp8_unpack_range, mxfp4_unpack_range
 
+        if self.fmt == "fp8":
+            return fp8_unpack_range(self.packed, self.src_bytes, self.chunk_bytes, self.elem_offset,
+                                    _numel(self.shape), self.block).view(self.shape)
         return mxfp4_unpack_range(self.packed, self.src_bytes, self.chunk_bytes, self.elem_offset,
                                   _numel(self.shape)).view(self.shape)
 
@@ -161,24 +173,37 @@ class PackedParam:
 Param = Union[torch.Tensor, PackedParam]
 
 
-def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int) -> Dict[str, PackedParam]:
-    """Named parameters of an MXFP4-packed layer blob (a uint8 tensor on any device,
-    the image of layer_nbytes(spec) source bytes in chunks of `chunk_bytes`; no copy)."""
-    from ..ops import mxfp4_packed_size
+def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, fmt: str = "mxfp4",
+                     block: int = 32) -> Dict[str, PackedParam]:
+    """Named parameters of a packed layer blob (a uint8 tensor on any device, the image of
+    layer_nbytes(spec) source bytes in chunks of `chunk_bytes`; no copy): MXFP4, or with
+    fmt="fp8" the fp8 format with one scale per `block` elements."""
+    from ..ops import fp8_packed_size, mxfp4_packed_size
 
     if packed.dtype != torch.uint8:
         raise ValueError("packed must be uint8")
+    if fmt not in ("mxfp4", "fp8"):
+        raise ValueError(f"fmt must be 'mxfp4' or 'fp8', not {fmt!r}")
     packed = packed.view(-1)
     src = layer_nbytes(spec)
-    if chunk_bytes <= 0 or chunk_bytes % 1024:
-        raise ValueError("chunk_bytes must be a positive multiple of 1024")
-    need = mxfp4_packed_size(src, chunk_bytes)
+    if fmt == "fp8":
+        if block not in (32, 64, 128, 256, 512):
+            raise ValueError("an fp8 scale block is 32, 64, 128, 256 or 512 elements")
+        if chunk_bytes <= 0 or chunk_bytes % (8 * block):
+            raise ValueError(f"chunk_bytes must be a positive multiple of 8 * block ({8 * block})")
+        need = fp8_packed_size(src, chunk_bytes, block)
+    else:
+        if block != 32:
+            raise ValueError("MXFP4 has a fixed scale block of 32 elements")
+        if chunk_bytes <= 0 or chunk_bytes % 1024:
+            raise ValueError("chunk_bytes must be a positive multiple of 1024")
+        need = mxfp4_packed_size(src, chunk_bytes)
     if packed.numel() < need:
         raise ValueError(f"packed holds {packed.numel()} B, the layer's packed image needs {need}")
     out = {}
     off = 0
     for name, shape in layer_params(spec):
-        out[name] = PackedParam(packed, src, chunk_bytes, off, tuple(shape))
+        out[name] = PackedParam(packed, src, chunk_bytes, off, tuple(shape), fmt, block)
         off += _numel(shape)
     return out
 
@@ -186,8 +211,11 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int) 
 def _linear(x: torch.Tensor, w: Param) -> torch.Tensor:
     """x @ w.T: from the packed bytes for a PackedParam, F.linear for a tensor."""
     if isinstance(w, PackedParam):
-        from ..ops import mxfp4_linear
+        from ..ops import fp8_linear, mxfp4_linear
 
+        if w.fmt == "fp8":
+            return fp8_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
+                              block=w.block, elem_offset=w.elem_offset, out_dtype=x.dtype)
         return mxfp4_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
                             elem_offset=w.elem_offset, out_dtype=x.dtype)
     return F.linear(x, w)
@@ -214,12 +242,13 @@ def _rope(x: torch.Tensor, theta: float) -> torch.Tensor:
 
 
 def _same_layer(*ws: Param) -> bool:
-    """All PackedParams over the same packed bytes with one layout."""
+    """All PackedParams over the same packed bytes with one format and layout."""
     if not all(isinstance(w, PackedParam) for w in ws):
         return False
     p0 = ws[0].packed
     return all(w.packed.device == p0.device and w.packed.data_ptr() == p0.data_ptr() and w.packed.numel() == p0.numel()
-               and w.src_bytes == ws[0].src_bytes and w.chunk_bytes == ws[0].chunk_bytes for w in ws[1:])
+               and w.src_bytes == ws[0].src_bytes and w.chunk_bytes == ws[0].chunk_bytes
+               and w.fmt == ws[0].fmt and w.block == ws[0].block for w in ws[1:])
 
 
 def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
@@ -230,19 +259,18 @@ def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
     if (fuse and h.is_cuda and _same_layer(wq, wk, wv) and wq.shape[1] == wk.shape[1] == wv.shape[1]
             and wk.elem_offset == wq.elem_offset + _numel(wq.shape)
             and wv.elem_offset == wk.elem_offset + _numel(wk.shape)):
-        from ..ops import mxfp4_linear
-
         nq, nk, nv = wq.shape[0], wk.shape[0], wv.shape[0]
-        y = mxfp4_linear(h, wq.packed, nq + nk + nv, wq.shape[1], src_bytes=wq.src_bytes, chunk_bytes=wq.chunk_bytes,
-                         elem_offset=wq.elem_offset, out_dtype=h.dtype)
+        y = _linear(h, PackedParam(wq.packed, wq.src_bytes, wq.chunk_bytes, wq.elem_offset, (nq + nk + nv, wq.shape[1]),
+                                   wq.fmt, wq.block))
         return y[..., :nq], y[..., nq:nq + nk], y[..., nq + nk:]
     return _linear(h, wq), _linear(h, wk), _linear(h, wv)
 
 
 def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool) -> torch.Tensor:
-    """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two PackedParams of one
-    layer with equal shapes (on the CPU the very ops of the other route)."""
-    if fuse and _same_layer(wg, wu) and wg.shape == wu.shape:
+    """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two MXFP4 PackedParams of
+    one layer with equal shapes (on the CPU the very ops of the other route). There is no
+    fused kernel for fp8: such parameters take one ops.fp8_linear each."""
+    if fuse and _same_layer(wg, wu) and wg.fmt == "mxfp4" and wg.shape == wu.shape:
         from ..ops import mxfp4_swiglu
 
         return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes,
@@ -253,10 +281,11 @@ def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool) -> torch.Tensor:
 def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
-    packed bytes (ops.mxfp4_linear), a packed norm weight is dequantized once. With
-    `fuse`, packed gate and up projections run as one ops.mxfp4_swiglu and, on the GPU,
-    packed q, k and v as one ops.mxfp4_linear; parameters that do not allow it (a mix
-    of tensors and PackedParams, other layouts) fall back per projection."""
+    packed bytes (ops.mxfp4_linear or ops.fp8_linear), a packed norm weight is
+    dequantized once. With `fuse`, MXFP4 gate and up projections run as one
+    ops.mxfp4_swiglu and, on the GPU, packed q, k and v of either format as one linear;
+    parameters that do not allow it (a mix of tensors and PackedParams or of formats,
+    other layouts) fall back per projection."""
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)

@@ -1,8 +1,8 @@
 """PyTorch-facing wrappers of the gfx950 kernels (csrc/kernels/*.hip).
 
 Every op takes and returns CUDA (HIP) tensors (the consumers of a packed
-layer, mxfp4_unpack_range, mxfp4_linear and mxfp4_swiglu, also take CPU tensors
-and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
+layer, mxfp4_unpack_range, mxfp4_linear, mxfp4_swiglu, fp8_unpack_range and
+fp8_linear, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
 dtypes, alignment and sizes are checked on the host before any launch (a kernel
 must never be handed a buffer smaller than its grid assumes).
 
@@ -19,6 +19,8 @@ must never be handed a buffer smaller than its grid assumes).
     y = ops.mxfp4_linear(h, p, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20)   # h @ w.T from the packed bytes
     z = ops.mxfp4_swiglu(h, p, 2048, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20,   # silu(h @ wg.T) * (h @ wu.T),
                          gate_offset=0, up_offset=2048 * 4096)                              # wg, wu = w[:2048], w[2048:]
+    p8 = ops.fp8_pack_layer(x, 64 << 20)                # the same layer fp8-packed (33/64 of the bytes at block 128)
+    y8 = ops.fp8_linear(h, p8, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20)   # h @ w.T from those bytes
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
 per-chunk CRC verification of every landed chunk); here they are usable on
@@ -52,6 +54,8 @@ __all__ = [
     "mxfp4_unpack_range",
     "mxfp4_linear",
     "mxfp4_swiglu",
+    "fp8_unpack_range",
+    "fp8_linear",
 ]
 
 _FP8_BLOCKS = (32, 64, 128, 256, 512)
@@ -430,6 +434,124 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
     _core.mxfp4_linear(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k, y.data_ptr(),
                        y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
+    return y if out is not None else y.view(*lead, n)
+
+
+def _check_fp8_layer(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, block: int) -> int:
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous 1-D uint8 tensor")
+    if block not in _FP8_BLOCKS:
+        raise ValueError(f"block must be one of {_FP8_BLOCKS}")
+    if chunk_bytes <= 0 or chunk_bytes % (8 * block):
+        raise ValueError(f"chunk_bytes must be a positive multiple of 8 * block ({8 * block}): packed chunks "
+                         "then start 16-byte aligned")
+    if src_bytes <= 0 or src_bytes % (2 * block):
+        raise ValueError(f"src_bytes must be a positive multiple of 2 * block ({2 * block})")
+    need = fp8_packed_size(src_bytes, chunk_bytes, block)
+    if packed.numel() < need:
+        raise ValueError(f"packed holds {packed.numel()} bytes, the layout needs {need}")
+    if packed.is_cuda and packed.data_ptr() % 16:
+        raise ValueError("packed must be 16-byte aligned")
+    return need
+
+
+def fp8_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, elem_offset: int, n: int,
+                     block: int = 128) -> torch.Tensor:
+    """Elements [elem_offset, elem_offset + n) of an fp8-packed layer (the chunked
+    layout of `fp8_pack_layer`) as bf16 [n], on `packed`'s device. Offset and count
+    are multiples of 32. GPU: the unpack kernel once per piece of a source chunk the
+    range touches (the whole blocks of the chunk in one launch; where the range starts
+    or ends inside a scale block, that part in power-of-two pieces), on the current
+    stream; CPU: the host reference."""
+    _check_fp8_layer(packed, src_bytes, chunk_bytes, block)
+    _check_range(src_bytes, elem_offset, n)
+    out = torch.empty(n, dtype=torch.bfloat16, device=packed.device)
+    if n == 0:
+        return out
+    if not packed.is_cuda:
+        _core.fp8_unpack_range_host(packed.data_ptr(), packed.numel(), src_bytes, chunk_bytes, block, elem_offset, n,
+                                    out.data_ptr())
+        return out
+    total, ce = src_bytes // 2, chunk_bytes // 2
+    pchunk = ce + ce // block * 4
+    e, end, stream = elem_offset, elem_offset + n, _stream()
+    while e < end:
+        c, r = divmod(e, ce)
+        nc = min(ce, total - c * ce)
+        lim = min(end - e, nc - r)
+        if r % block == 0 and lim >= block:
+            take, blk = lim // block * block, block  # whole scale blocks
+        else:
+            # part of one scale block: the kernel wants whole blocks, so a power-of-two piece
+            # (32 at least) goes as one block of its own length with that block's scale
+            take = blk = 1 << (min(lim, block - r % block).bit_length() - 1)
+        base = packed.data_ptr() + c * pchunk
+        # r and e - elem_offset are multiples of 32: q 16-B (at least), the output 64-B aligned
+        _core.fp8_unpack(base + r, base + nc + 4 * (r // block), take, out.data_ptr() + 2 * (e - elem_offset), blk,
+                         stream)
+        e += take
+    return out
+
+
+def fp8_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
+               chunk_bytes: int, block: int = 128, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
+               split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
+    weight stored as elements [elem_offset, ...) of the fp8-packed layer `packed`
+    (`src_bytes` of bf16 in chunks of `chunk_bytes` with one scale per `block` elements,
+    the layout of `fp8_pack_layer`).
+
+    GPU: one kernel on the current stream reads the e4m3 codes and the block scales
+    where they lie, dequantizes in registers and accumulates in f32 on the bf16 MFMA;
+    no bf16 copy of the weight is made. `split_k`, `row_tiles`, `out` and the
+    determinism are `mxfp4_linear`'s. CPU: the host reference dequantizes the range,
+    then ``F.linear`` - in f32 for an f32 result, in bf16 for a bf16 one.
+    in_features and elem_offset are multiples of 32, out_features of 16, and
+    chunk_bytes of 8 * block (every packed chunk then starts 16-byte aligned; the
+    engine's chunk sizes do)."""
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"x must be {torch.bfloat16}, got {x.dtype}")
+    n, k = int(out_features), int(in_features)
+    if n <= 0 or n % 16 or k <= 0 or k % 32:
+        raise ValueError("out_features must be a positive multiple of 16 and in_features of 32")
+    if x.dim() < 1 or x.shape[-1] != k or x.numel() == 0:
+        raise ValueError(f"x must be [..., {k}] with at least one row, got {tuple(x.shape)}")
+    if x.device != packed.device:
+        raise ValueError("x and packed must be on the same device")
+    if not 0 <= split_k <= 16:
+        raise ValueError("split_k must be in 0..16")
+    if row_tiles not in (0, 1, 2, 4) or (row_tiles and n // 16 % row_tiles):
+        raise ValueError("row_tiles must be 0, 1, 2 or 4 and divide out_features / 16")
+    _check_fp8_layer(packed, src_bytes, chunk_bytes, block)
+    _check_range(src_bytes, elem_offset, n * k)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, k)
+    if not x.is_cuda:
+        if out is not None:
+            raise ValueError("out is for GPU tensors")
+        w = fp8_unpack_range(packed, src_bytes, chunk_bytes, elem_offset, n * k, block).view(n, k)
+        if out_dtype == torch.float32:
+            y = torch.nn.functional.linear(x2.float(), w.float())
+        else:
+            y = torch.nn.functional.linear(x2, w)
+        return y.view(*lead, n)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() % 16:
+        x2 = x2.clone()
+    m = x2.shape[0]
+    if out is None:
+        y = torch.empty(m, n, dtype=out_dtype, device=x.device)
+    else:
+        y = out
+        if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
+            raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    _core.fp8_linear(packed.data_ptr(), src_bytes, chunk_bytes, block, elem_offset, x2.data_ptr(), m, n, k,
+                     y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
 
 

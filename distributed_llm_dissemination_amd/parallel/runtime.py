@@ -1220,6 +1220,17 @@ class Runtime:
             return unflatten(torch.frombuffer(bytearray(self.unpacked_layer_bytes(layer)), dtype=torch.uint8), spec)
         return unflatten(self.layer_tensor(layer, unpacked=True), spec)
 
+    def packed_layer_params(self, layer: int, spec):
+        """A PackedParam per name over layer_tensor(layer), for --store packed with
+        --pack mxfp4 or --pack fp8 (the latter with this session's scale block): the
+        packed slot itself on the rccl engine, with no bf16 image, for decoder_forward
+        to use in place - ops.mxfp4_linear / ops.mxfp4_swiglu, or ops.fp8_linear."""
+        from ..models.weights import unflatten_packed
+
+        if self.pack not in ("mxfp4", "fp8") or self.store != "packed":
+            raise ValueError("packed parameters need --store packed with --pack mxfp4 or --pack fp8")
+        return unflatten_packed(self.layer_tensor(layer), spec, self.chunk_bytes, self.pack, self.pack_block)
+
     def close(self) -> None:
         self._closed = True
         if self.engine is not None:
