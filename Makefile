@@ -3,6 +3,7 @@
 #   make            -> distributed_llm_dissemination_amd/_core<ext>.so  (C++ core + HIP kernels + RCCL engine)
 #   make tools      -> bin/diskspeed (NVMe -> pinned -> HBM calibration)
 #   make sanitize   -> build/tests/*_{tsan,asan} (host-only core under Thread/Address sanitizer)
+#   make sanitize-mxfp6 -> build/tests/mxfp6_selftest_asan (the MXFP6 host codec under ASan + UBSan), and runs it
 #
 # The extension links the HIP runtime and RCCL that PyTorch-ROCm ships, so one
 # process never holds two HIP runtimes (torch is imported before _core).
@@ -29,7 +30,7 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Icsrc -I$(ROCM)/includ
              -fvisibility=hidden
 LDFLAGS   := -shared -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64 -lrccl -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lrocprofiler-sdk-roctx -lpthread
 
-CORE_SRC  := csrc/core/vclock.cc csrc/core/json.cc csrc/core/log.cc csrc/core/wire.cc csrc/core/crc32c.cc csrc/core/fp8.cc csrc/core/mxfp4.cc csrc/core/trace.cc csrc/transport/inproc.cc \
+CORE_SRC  := csrc/core/vclock.cc csrc/core/json.cc csrc/core/log.cc csrc/core/wire.cc csrc/core/crc32c.cc csrc/core/fp8.cc csrc/core/mxfp4.cc csrc/core/mxfp6.cc csrc/core/trace.cc csrc/transport/inproc.cc \
              csrc/transport/tcp.cc csrc/store/store.cc csrc/sched/maxflow.cc csrc/sched/lp.cc csrc/roles/node.cc \
              csrc/roles/mode01.cc csrc/roles/mode2.cc csrc/roles/mode3.cc csrc/roles/multihost.cc \
              csrc/roles/recovery.cc csrc/roles/dispatch.cc \
@@ -64,7 +65,7 @@ bin/contention: $(BUILD)/tools/contention.hip.o $(BUILD)/kernels/crc32c.hip.o $(
 	$(HIPCC) --offload-arch=$(ARCH) -o $@ $^ -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64 -lrccl \
 	  -L$(ROCM)/lib -Wl,-rpath,$(ROCM)/lib
 
-bin/cvtprobe: csrc/tools/cvtprobe.hip csrc/kernels/mxfp4_cvt.h
+bin/cvtprobe: csrc/tools/cvtprobe.hip csrc/kernels/mxfp4_cvt.h csrc/kernels/mxfp6_cvt.h
 	@mkdir -p bin
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -Icsrc -Wno-unused-value -Wno-unused-result -o $@ $< -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64
 
@@ -92,7 +93,19 @@ $(BUILD)/tests/core_selftest_asan: $(SAN_SRC)
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-omit-frame-pointer -I/opt/rocm/include -o $@ $(SAN_SRC) -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lrocprofiler-sdk-roctx -lpthread
 
+# The MXFP6 host codec alone (core/mxfp6.cc) with its own main: exact-size heap
+# buffers, so a 6-bit extraction past a block or a chunk is an ASan report. The
+# sanitizer runtimes are linked statically: the program runs as it is, whatever
+# the environment preloads.
+$(BUILD)/tests/mxfp6_selftest_asan: csrc/tests/mxfp6_selftest.cc csrc/core/mxfp6.cc csrc/core/mxfp6.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	  -static-libasan -static-libubsan -o $@ csrc/tests/mxfp6_selftest.cc csrc/core/mxfp6.cc
+
+sanitize-mxfp6: $(BUILD)/tests/mxfp6_selftest_asan
+	$(BUILD)/tests/mxfp6_selftest_asan
+
 clean:
 	rm -rf $(BUILD) $(PKG)/_core*.so bin/diskspeed bin/h2dbench bin/contention
 
-.PHONY: all tools sanitize clean
+.PHONY: all tools sanitize sanitize-mxfp6 clean

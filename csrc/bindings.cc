@@ -9,6 +9,7 @@
 #include "core/crc32c.h"
 #include "core/fp8.h"
 #include "core/mxfp4.h"
+#include "core/mxfp6.h"
 #include "core/log.h"
 #include "core/ratelimit.h"
 #include "core/trace.h"
@@ -600,6 +601,69 @@ PYBIND11_MODULE(_core, m) {
                              reinterpret_cast<uint16_t*>(out));
   }, py::arg("packed"), py::arg("packed_bytes"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"),
      py::arg("n"), py::arg("out"));
+  // MXFP6 wire/storage format (core/mxfp6.h), host reference: the same entry points
+  m.def("mxfp6_packed_size", &mxfp6::packed_size, py::arg("src_bytes"), py::arg("src_chunk"));
+  m.def("mxfp6_source_size", &mxfp6::source_size, py::arg("packed"), py::arg("src_chunk"));
+  m.def("mxfp6_pack_layer_host", [](py::bytes src, int64_t src_chunk) {
+    std::string s(src);
+    mxfp6::check(int64_t(s.size()), src_chunk);
+    std::string out(size_t(mxfp6::packed_size(int64_t(s.size()), src_chunk)), '\0');
+    {
+      py::gil_scoped_release nogil;
+      mxfp6::pack_layer_host(reinterpret_cast<const uint8_t*>(s.data()), int64_t(s.size()), src_chunk,
+                             reinterpret_cast<uint8_t*>(out.data()));
+    }
+    return py::bytes(out);
+  }, py::arg("src"), py::arg("src_chunk"));
+  m.def("mxfp6_pack_layer_into", [](uint64_t src, int64_t src_bytes, int64_t src_chunk, uint64_t dst) {
+    py::gil_scoped_release nogil;
+    mxfp6::pack_layer_host(reinterpret_cast<const uint8_t*>(src), src_bytes, src_chunk,
+                           reinterpret_cast<uint8_t*>(dst));
+  });
+  m.def("mxfp6_unpack_layer_host", [](py::bytes packed, int64_t src_bytes, int64_t src_chunk) {
+    std::string s(packed);
+    mxfp6::check(src_bytes, src_chunk);
+    if (int64_t(s.size()) != mxfp6::packed_size(src_bytes, src_chunk))
+      throw std::runtime_error("packed buffer size does not match src_bytes");
+    std::string out(size_t(src_bytes), '\0');
+    {
+      py::gil_scoped_release nogil;
+      mxfp6::unpack_layer_host(reinterpret_cast<const uint8_t*>(s.data()), src_bytes, src_chunk,
+                               reinterpret_cast<uint8_t*>(out.data()));
+    }
+    return py::bytes(out);
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"));
+  // one chunk: n bf16 (n a multiple of 32) -> (q bytes, scale bytes), and back
+  m.def("mxfp6_pack_host", [](py::bytes bf16) {
+    std::string s(bf16);
+    if (s.size() % 64) throw std::runtime_error("mxfp6 packing needs a multiple of 32 bf16 values");
+    const int64_t n = int64_t(s.size()) / 2;
+    std::string q(size_t(n / 32 * 24), '\0'), sc(size_t(n / 32), '\0');
+    mxfp6::pack_host(reinterpret_cast<const uint16_t*>(s.data()), n, reinterpret_cast<uint8_t*>(q.data()),
+                     reinterpret_cast<uint8_t*>(sc.data()));
+    return py::make_tuple(py::bytes(q), py::bytes(sc));
+  }, py::arg("bf16"));
+  m.def("mxfp6_unpack_host", [](py::bytes q, py::bytes scales) {
+    std::string qs(q), ss(scales);
+    if (qs.size() != ss.size() * 24) throw std::runtime_error("mxfp6 q must hold 24 bytes per scale byte");
+    const int64_t n = int64_t(ss.size()) * 32;
+    std::string out(size_t(n) * 2, '\0');
+    mxfp6::unpack_host(reinterpret_cast<const uint8_t*>(qs.data()), reinterpret_cast<const uint8_t*>(ss.data()), n,
+                       reinterpret_cast<uint16_t*>(out.data()));
+    return py::bytes(out);
+  }, py::arg("q"), py::arg("scales"));
+  // elements [elem_off, elem_off + n) of a packed layer in host memory at `packed` -> n bf16 at `out`
+  m.def("mxfp6_unpack_range_host", [](uint64_t packed, int64_t packed_bytes, int64_t src_bytes, int64_t src_chunk,
+                                      int64_t elem_off, int64_t n, uint64_t out) {
+    mxfp6::check(src_bytes, src_chunk);
+    if (packed_bytes < mxfp6::packed_size(src_bytes, src_chunk))
+      throw std::runtime_error("packed buffer is smaller than the layer's packed size");
+    py::gil_scoped_release nogil;
+    mxfp6::unpack_range_host(reinterpret_cast<const uint8_t*>(packed), src_bytes, src_chunk, elem_off, n,
+                             reinterpret_cast<uint16_t*>(out));
+  }, py::arg("packed"), py::arg("packed_bytes"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"),
+     py::arg("n"), py::arg("out"));
+  m.def("mxfp6_scale_exp", &mxfp6::scale_exp, py::arg("amax_f32_bits"));
 
   // ---- roles
   py::class_<NodeConfig>(m, "NodeConfig")

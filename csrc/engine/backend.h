@@ -32,8 +32,8 @@ namespace dissem {
 
 using Ev = uint64_t;  // 0 = no event
 
-// Packed wire/storage formats (PlannedConfig::pack): core/fp8.h, core/mxfp4.h.
-constexpr int kPackFp8 = 1, kPackMxfp4 = 2;
+// Packed wire/storage formats (PlannedConfig::pack): core/fp8.h, core/mxfp4.h, core/mxfp6.h.
+constexpr int kPackFp8 = 1, kPackMxfp4 = 2, kPackMxfp6 = 3;
 
 struct XOp {
   bool send;
@@ -58,7 +58,7 @@ class Backend {
   virtual Ev stage(uint8_t* dst, const uint8_t* src_host, int64_t n) = 0;
   // copy queue: host -> device copy of `n_src` bytes of bf16, then pack them
   // into dst in the packed chunk layout of `format` (core/fp8.h with `block`
-  // elements per scale, or core/mxfp4.h, whose block is 32)
+  // elements per scale, or core/mxfp4.h or core/mxfp6.h, whose block is 32)
   virtual Ev stage_pack(uint8_t* dst, const uint8_t* src_host, int64_t n_src, int block, int format = kPackFp8) = 0;
   // Independent comm lanes (>= 1).
   virtual int lanes() const { return 1; }
@@ -79,9 +79,13 @@ class Backend {
   // one event (one launch per kCrcBatchMax requests on GPUs, the fold inside
   // it): the CRC32C of [p, p+n) into result slot `slot`. A request with `out`
   // is a packed chunk (`format`: the core/fp8.h layout of `n` bf16 SOURCE bytes
-  // with `block`-element scales, or the core/mxfp4.h one): its packed bytes are
-  // checked and dequantized to `out` in the same pass (the fused kernel). No
-  // requests: an ordering marker on the verify queue.
+  // with `block`-element scales, or the core/mxfp4.h or core/mxfp6.h one): its
+  // packed bytes are checked and dequantized to `out` inside the same event. On
+  // GPUs fp8 and MXFP4 do both in one pass over the packed bytes (the fused
+  // kernel); MXFP6, whose 24-byte blocks do not divide the CRC walk's 16-byte
+  // words, runs the CRC-only batch walk and then a batched unpack kernel on the
+  // same stream, so its packed bytes are read twice. No requests: an ordering
+  // marker on the verify queue.
   struct CheckReq {
     const uint8_t* p;
     int64_t n;

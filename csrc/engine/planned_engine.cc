@@ -39,6 +39,7 @@
 
 #include "core/fp8.h"
 #include "core/mxfp4.h"
+#include "core/mxfp6.h"
 #include "core/log.h"
 #include "core/queue.h"
 #include "core/trace.h"
@@ -83,10 +84,14 @@ PlannedEngine::PlannedEngine(const PlannedConfig& cfg, std::unique_ptr<Backend> 
     cfg_.pack_block = mxfp4::kBlock;
     mxfp4::check(cfg_.chunk_bytes, cfg_.chunk_bytes);
     grid_ = mxfp4::packed_chunk(cfg_.chunk_bytes);
+  } else if (cfg_.pack == kPackMxfp6) {
+    cfg_.pack_block = mxfp6::kBlock;
+    mxfp6::check(cfg_.chunk_bytes, cfg_.chunk_bytes);
+    grid_ = mxfp6::packed_chunk(cfg_.chunk_bytes);
   } else if (cfg_.pack != 0) {
     throw std::runtime_error("unknown pack format " + std::to_string(cfg_.pack));
   }
-  if (cfg_.unpack_store && cfg_.pack == 0) throw std::runtime_error("unpack_store needs pack = fp8 or mxfp4");
+  if (cfg_.unpack_store && cfg_.pack == 0) throw std::runtime_error("unpack_store needs pack = fp8, mxfp4 or mxfp6");
   inject_rng_.seed(cfg_.inject_seed * 0x9E3779B97F4A7C15ull + uint64_t(cfg_.rank));
   lanes_ = std::max(1, backend_->lanes());
   ops_.resize(size_t(lanes_));
@@ -202,10 +207,15 @@ int64_t PlannedEngine::slot_size(int64_t src_bytes) const {
     mxfp4::check(src_bytes, cfg_.chunk_bytes);
     return mxfp4::packed_size(src_bytes, cfg_.chunk_bytes);
   }
+  if (cfg_.pack == kPackMxfp6) {
+    mxfp6::check(src_bytes, cfg_.chunk_bytes);
+    return mxfp6::packed_size(src_bytes, cfg_.chunk_bytes);
+  }
   return src_bytes;
 }
 
 int64_t PlannedEngine::source_size(int64_t packed) const {
+  if (cfg_.pack == kPackMxfp6) return mxfp6::source_size(packed, cfg_.chunk_bytes);
   return cfg_.pack == kPackMxfp4 ? mxfp4::source_size(packed, cfg_.chunk_bytes)
                                  : fp8::source_size(packed, cfg_.chunk_bytes, cfg_.pack_block);
 }

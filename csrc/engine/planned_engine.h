@@ -86,8 +86,8 @@ struct PlannedConfig {
   // fp8 wire/storage format (core/fp8.h): layers are staged from bf16 sources
   // and packed on the copy queue; HBM slots, transfers and CRCs use the packed
   // chunk grid. chunk_bytes stays the SOURCE (bf16) chunk.
-  int pack = 0;                    // 0 none, 1 fp8 e4m3fn block-scaled, 2 MXFP4 (core/mxfp4.h)
-  int pack_block = 128;            // elements per scale (MXFP4: forced to 32)
+  int pack = 0;                    // 0 none, 1 fp8 e4m3fn block-scaled, 2 MXFP4 (core/mxfp4.h), 3 MXFP6 (core/mxfp6.h)
+  int pack_block = 128;            // elements per scale (MXFP4, MXFP6: forced to 32)
   // pack != 0 only: every chunk that becomes resident (received or staged) is
   // also dequantized to bf16 into a second HBM slot of the layer by the fused
   // verify+unpack kernel - the CRC check and the dequantization in one pass

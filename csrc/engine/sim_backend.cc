@@ -35,6 +35,7 @@
 #include "core/crc32c.h"
 #include "core/fp8.h"
 #include "core/mxfp4.h"
+#include "core/mxfp6.h"
 #include "core/queue.h"
 #include "core/vclock.h"
 #include "engine/backend.h"
@@ -349,6 +350,8 @@ class SimBackend : public Backend {
       const double t0 = vclock::now();
       const int64_t n = n_src / 2;
       if (copy && format == kPackMxfp4) mxfp4::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, dst + n / 2);
+      else if (copy && format == kPackMxfp6)
+        mxfp6::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, dst + n / mxfp6::kBlock * mxfp6::kBlockBytes);
       else if (copy) fp8::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, reinterpret_cast<float*>(dst + n), block);
       stage_delay(t0, n_src);
       ev->set(1);
@@ -474,6 +477,7 @@ class SimBackend : public Backend {
   }
 
   static int64_t packed_len(const CheckReq& r) {  // packed bytes of a fused request
+    if (r.format == kPackMxfp6) return mxfp6::packed_len(r.n);
     return r.format == kPackMxfp4 ? mxfp4::packed_len(r.n) : fp8::packed_len(r.n, r.block);
   }
 
@@ -512,6 +516,8 @@ class SimBackend : public Backend {
         results_[r.slot] = crc32c(r.p, size_t(packed_len(r)));
         if (r.format == kPackMxfp4)
           mxfp4::unpack_host(r.p, r.p + n / 2, n, reinterpret_cast<uint16_t*>(r.out));
+        else if (r.format == kPackMxfp6)
+          mxfp6::unpack_host(r.p, r.p + n / mxfp6::kBlock * mxfp6::kBlockBytes, n, reinterpret_cast<uint16_t*>(r.out));
         else
           fp8::unpack_host(r.p, reinterpret_cast<const float*>(r.p + n), n, reinterpret_cast<uint16_t*>(r.out), r.block);
       }

@@ -19,6 +19,7 @@
 #include "core/crc32c.h"
 #include "core/fp8.h"
 #include "core/mxfp4.h"
+#include "core/mxfp6.h"
 #include "gpu/gpu_api.h"
 #include "gpu/hip_backend.h"
 #include "kernels/kernels.h"
@@ -483,6 +484,62 @@ void register_gpu_bindings(PyObject* module) {
     auto v = fused_items(items, reinterpret_cast<uint32_t*>(crc_out_dev));
     check(kern::mxfp4_verify_unpack_batch(v.data(), int(v.size()), reinterpret_cast<void*>(ws), as_stream(stream), cus),
           "mxfp4_verify_unpack_batch");
+  }, py::arg("items"), py::arg("crc_out"), py::arg("ws"), py::arg("stream") = 0, py::arg("cus") = 0);
+  // ---- MXFP6 (core/mxfp6.h): the same entry points as MXFP4
+  m.def("mxfp6_pack", [](uint64_t bf16, int64_t n, uint64_t q, uint64_t scales, uint64_t stream) {
+    check(kern::mxfp6_pack(reinterpret_cast<const uint16_t*>(bf16), n, reinterpret_cast<uint8_t*>(q),
+                           reinterpret_cast<uint8_t*>(scales), as_stream(stream)),
+          "mxfp6_pack");
+  }, py::arg("bf16"), py::arg("n"), py::arg("q"), py::arg("scales"), py::arg("stream") = 0);
+  m.def("mxfp6_unpack", [](uint64_t q, uint64_t scales, int64_t n, uint64_t bf16, uint64_t stream) {
+    check(kern::mxfp6_unpack(reinterpret_cast<const uint8_t*>(q), reinterpret_cast<const uint8_t*>(scales), n,
+                             reinterpret_cast<uint16_t*>(bf16), as_stream(stream)),
+          "mxfp6_unpack");
+  }, py::arg("q"), py::arg("scales"), py::arg("n"), py::arg("bf16"), py::arg("stream") = 0);
+  m.def("mxfp6_pack_chunks", [](uint64_t src, int64_t src_bytes, int64_t src_chunk, uint64_t dst, uint64_t stream) {
+    check(kern::mxfp6_pack_chunks(reinterpret_cast<const void*>(src), src_bytes, src_chunk,
+                                  reinterpret_cast<void*>(dst), as_stream(stream)),
+          "mxfp6_pack_chunks");
+  }, py::arg("src"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("dst"), py::arg("stream") = 0);
+  m.def("mxfp6_verify_unpack_async", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, uint64_t out,
+                                        uint64_t crc_out_dev, uint64_t ws, uint64_t stream, int cus) {
+    check(kern::mxfp6_verify_unpack(reinterpret_cast<const void*>(packed), src_bytes, src_chunk,
+                                    reinterpret_cast<uint16_t*>(out), reinterpret_cast<uint32_t*>(crc_out_dev),
+                                    reinterpret_cast<void*>(ws), as_stream(stream), cus),
+          "mxfp6_verify_unpack");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("out"), py::arg("crc_out"), py::arg("ws"),
+     py::arg("stream") = 0, py::arg("cus") = 0);
+  // synchronous: writes the bf16 layer to `out`, returns the CRC32C of every packed chunk
+  m.def("mxfp6_verify_unpack", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, uint64_t out, uint64_t stream,
+                                  int cus) {
+    py::gil_scoped_release nogil;
+    mxfp6::check(src_bytes, src_chunk);
+    const int64_t pbytes = mxfp6::packed_size(src_bytes, src_chunk);
+    const int64_t pchunk = mxfp6::packed_chunk(src_chunk);
+    const size_t n = size_t((pbytes + pchunk - 1) / pchunk);
+    void* ws = nullptr;
+    uint32_t *host = nullptr, *dev = nullptr;
+    const size_t wsb = kern::crc32c_workspace_bytes(pbytes, pchunk);
+    check(hipMalloc(&ws, wsb), "hipMalloc");
+    check(hipMemset(ws, 0, wsb), "hipMemset");
+    check(hipHostMalloc(reinterpret_cast<void**>(&host), std::max<size_t>(n, 1) * 4, hipHostMallocMapped),
+          "hipHostMalloc");
+    check(hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0), "hipHostGetDevicePointer");
+    hipError_t e = kern::mxfp6_verify_unpack(reinterpret_cast<const void*>(packed), src_bytes, src_chunk,
+                                             reinterpret_cast<uint16_t*>(out), dev, ws, as_stream(stream), cus);
+    if (e == hipSuccess) e = hipStreamSynchronize(as_stream(stream));
+    std::vector<uint32_t> crc(host, host + n);
+    (void)hipFree(ws);
+    (void)hipHostFree(host);
+    check(e, "mxfp6_verify_unpack");
+    return crc;
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("out"), py::arg("stream") = 0,
+     py::arg("cus") = 0);
+  m.def("mxfp6_verify_unpack_batch_async",[fused_items](const std::vector<std::tuple<uint64_t, int64_t, uint64_t>>& items,
+                                                         uint64_t crc_out_dev, uint64_t ws, uint64_t stream, int cus) {
+    auto v = fused_items(items, reinterpret_cast<uint32_t*>(crc_out_dev));
+    check(kern::mxfp6_verify_unpack_batch(v.data(), int(v.size()), reinterpret_cast<void*>(ws), as_stream(stream), cus),
+          "mxfp6_verify_unpack_batch");
   }, py::arg("items"), py::arg("crc_out"), py::arg("ws"), py::arg("stream") = 0, py::arg("cus") = 0);
   // W4A16 linear from the packed layer in place (kernels/mxfp4_linear.hip); stream-ordered
   m.def("mxfp4_linear", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,

@@ -267,6 +267,8 @@ class HipBackend : public Backend {
     const int64_t n = n_src / 2;
     if (format == kPackMxfp4)
       HIP_OK(kern::mxfp4_pack(static_cast<const uint16_t*>(scratch_[q]), n, dst, dst + n / 2, s));
+    else if (format == kPackMxfp6)
+      HIP_OK(kern::mxfp6_pack(static_cast<const uint16_t*>(scratch_[q]), n, dst, dst + n / 32 * 24, s));
     else
       HIP_OK(kern::fp8_pack(static_cast<const uint16_t*>(scratch_[q]), n, dst, reinterpret_cast<float*>(dst + n), block,
                             s));
@@ -333,6 +335,8 @@ class HipBackend : public Backend {
     auto flush_fused = [&] {
       if (!fused.empty() && format == kPackMxfp4)
         HIP_OK(kern::mxfp4_verify_unpack_batch(fused.data(), int(fused.size()), ws_, verify_, verify_cus_));
+      else if (!fused.empty() && format == kPackMxfp6)
+        HIP_OK(kern::mxfp6_verify_unpack_batch(fused.data(), int(fused.size()), ws_, verify_, verify_cus_));
       else if (!fused.empty())
         HIP_OK(kern::fp8_verify_unpack_batch(fused.data(), int(fused.size()), block, ws_, verify_, verify_cus_));
       fused.clear();

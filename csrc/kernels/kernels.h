@@ -99,6 +99,22 @@ hipError_t mxfp4_verify_unpack(const void* packed, int64_t src_bytes, int64_t sr
                                uint32_t* crc_out, void* workspace, hipStream_t s, int cus = 0);
 hipError_t mxfp4_verify_unpack_batch(const FusedItem* items, int n, void* workspace, hipStream_t s, int cus = 0);
 
+// ---- mxfp6.hip: bf16 -> MXFP6 (e2m3 codes, 24 bytes per 32 elements, element i
+// at bits [6i, 6i + 6) of its block; one E8M0 scale byte per 32 elements;
+// core/mxfp6.h) and back, bit-exact with the host reference. n a multiple of 32;
+// bf16 16-B, q 8-B aligned. Nothing allocated, the caller's stream.
+hipError_t mxfp6_pack(const uint16_t* bf16, int64_t n, uint8_t* q, uint8_t* scales, hipStream_t s);
+hipError_t mxfp6_unpack(const uint8_t* q, const uint8_t* scales, int64_t n, uint16_t* bf16, hipStream_t s);
+// Whole layer into the chunked packed layout of core/mxfp6.h (one pack launch per chunk).
+hipError_t mxfp6_pack_chunks(const void* src, int64_t src_bytes, int64_t src_chunk, void* dst, hipStream_t s);
+// Verify + unpack of MXFP6-packed layers and chunks: arguments, workspace and
+// results as for the MXFP4 pair (src_chunk a multiple of 4096, src_bytes and
+// every src_len a multiple of 64). Two launches on `s`: the CRC-only walk, then
+// a grid-stride unpack sized to `cus` - the packed bytes are read twice.
+hipError_t mxfp6_verify_unpack(const void* packed, int64_t src_bytes, int64_t src_chunk, uint16_t* out,
+                               uint32_t* crc_out, void* workspace, hipStream_t s, int cus = 0);
+hipError_t mxfp6_verify_unpack_batch(const FusedItem* items, int n, void* workspace, hipStream_t s, int cus = 0);
+
 // ---- mxfp4_linear.hip: y[m][n] = sum_k x[m][k] * W[n][k] with W read in place
 // from an MXFP4-packed layer (no bf16 copy of W): W is a row-major [N, K]
 // parameter whose element 0 is element `elem_off` of the layer of `src_bytes`

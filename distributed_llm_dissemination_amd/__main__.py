@@ -64,12 +64,15 @@ def build_parser() -> argparse.ArgumentParser:
                    help="data plane: host (TCP into RAM, the reference) or rccl (RCCL/xGMI into HBM); "
                         "auto = rccl under torchrun with a GPU visible, else host")
     p.add_argument("--chunk-mib", type=int, default=64)
-    p.add_argument("--pack", default="none", choices=["none", "fp8", "mxfp4"],
+    p.add_argument("--pack", default="none", choices=["none", "fp8", "mxfp4", "mxfp6"],
                    help="fp8: bf16 layers are packed to block-scaled e4m3fn on staging (wire + HBM format); "
-                        "mxfp4: to OCP MXFP4 (e2m1 codes, one E8M0 scale per 32 values; 17/64 of the bf16 bytes)")
+                        "mxfp4: to OCP MXFP4 (e2m1 codes, one E8M0 scale per 32 values; 17/64 of the bf16 bytes); "
+                        "mxfp6: to OCP MXFP6 (e2m3 codes, 24 bytes and one E8M0 scale per 32 values; 25/64 of the "
+                        "bf16 bytes, fp8-class error)")
     p.add_argument("--store", default="packed", choices=["packed", "bf16"],
-                   help="with --pack fp8 or mxfp4: bf16 = also keep each layer dequantized to bf16 in HBM (fused "
-                        "verify+unpack kernel on every landed chunk)")
+                   help="with --pack fp8, mxfp4 or mxfp6: bf16 = also keep each layer dequantized to bf16 in HBM "
+                        "(verify+unpack of every landed chunk: one fused kernel for fp8 and mxfp4, the CRC walk "
+                        "and an unpack kernel for mxfp6)")
     p.add_argument("--verify", default="crc32c", choices=["none", "crc32c"])
     p.add_argument("--weights", default="", metavar="PRESET",
                    help="layers hold random-init decoder-layer weights of this model (models/weights.py presets: "
@@ -328,7 +331,9 @@ def _check_weights(rt, spec, layers, my_id: int) -> None:
     seeded weights. With --pack mxfp4 --store packed the pass runs from the packed
     slot (ops.mxfp4_linear for q/k/v, o and down, ops.mxfp4_swiglu for the gated
     front half of the MLP), with no bf16 copy of the weights; with --pack fp8
-    --store packed likewise, through ops.fp8_linear."""
+    --store packed likewise, through ops.fp8_linear. With --pack mxfp6 --store
+    packed every projection dequantizes its parameter from the slot
+    (ops.mxfp6_unpack_range) and multiplies: there is no in-place MXFP6 kernel yet."""
     import torch
 
     from .models.weights import decoder_forward, random_layer

@@ -29,6 +29,11 @@ scale block, and ``decoder_forward`` runs the layer from the e4m3 codes and bloc
 five weight launches: q/k/v as one ``ops.fp8_linear``, ``o_proj``, gate, up (there is no fused
 fp8 SwiGLU; ``silu(g) * u`` is plain torch) and ``down_proj``.
 
+``--pack mxfp6 --store packed`` gives ``PackedParam``s with ``fmt="mxfp6"`` from the same
+call. There is no in-place MXFP6 kernel yet: every projection dequantizes its parameter
+from the slot (``ops.mxfp6_unpack_range``; on the GPU the merged q/k/v in one piece) and
+multiplies with ``F.linear``, so the slot stays the only resident copy of the weights.
+
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
 on received weights against the originals.
@@ -143,8 +148,8 @@ def unflatten(blob: torch.Tensor, spec: DecoderSpec) -> Dict[str, torch.Tensor]:
 
 @dataclass(frozen=True)
 class PackedParam:
-    """One parameter of a layer that is held packed - `fmt` "mxfp4" (core/mxfp4.h) or
-    "fp8" (core/fp8.h, one scale per `block` elements): elements [elem_offset,
+    """One parameter of a layer that is held packed - `fmt` "mxfp4" (core/mxfp4.h),
+    "mxfp6" (core/mxfp6.h) or "fp8" (core/fp8.h, one scale per `block` elements): elements [elem_offset,
     elem_offset + numel) of the layer of `src_bytes` bf16 bytes whose packed image, in
     chunks of `chunk_bytes`, is `packed`. A view: nothing is copied."""
     packed: torch.Tensor
@@ -161,11 +166,14 @@ class PackedParam:
 
     def dequantize(self) -> torch.Tensor:
         """The parameter as a bf16 tensor on the packed tensor's device."""
-        from ..ops import fp8_unpack_range, mxfp4_unpack_range
+        from ..ops import fp8_unpack_range, mxfp4_unpack_range, mxfp6_unpack_range
 
         if self.fmt == "fp8":
             return fp8_unpack_range(self.packed, self.src_bytes, self.chunk_bytes, self.elem_offset,
                                     _numel(self.shape), self.block).view(self.shape)
+        if self.fmt == "mxfp6":
+            return mxfp6_unpack_range(self.packed, self.src_bytes, self.chunk_bytes, self.elem_offset,
+                                      _numel(self.shape)).view(self.shape)
         return mxfp4_unpack_range(self.packed, self.src_bytes, self.chunk_bytes, self.elem_offset,
                                   _numel(self.shape)).view(self.shape)
 
@@ -176,14 +184,15 @@ Param = Union[torch.Tensor, PackedParam]
 def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, fmt: str = "mxfp4",
                      block: int = 32) -> Dict[str, PackedParam]:
     """Named parameters of a packed layer blob (a uint8 tensor on any device, the image of
-    layer_nbytes(spec) source bytes in chunks of `chunk_bytes`; no copy): MXFP4, or with
-    fmt="fp8" the fp8 format with one scale per `block` elements."""
-    from ..ops import fp8_packed_size, mxfp4_packed_size
+    layer_nbytes(spec) source bytes in chunks of `chunk_bytes`; no copy): MXFP4, with
+    fmt="mxfp6" MXFP6 (block 32 as well), or with fmt="fp8" the fp8 format with one scale
+    per `block` elements."""
+    from ..ops import fp8_packed_size, mxfp4_packed_size, mxfp6_packed_size
 
     if packed.dtype != torch.uint8:
         raise ValueError("packed must be uint8")
-    if fmt not in ("mxfp4", "fp8"):
-        raise ValueError(f"fmt must be 'mxfp4' or 'fp8', not {fmt!r}")
+    if fmt not in ("mxfp4", "mxfp6", "fp8"):
+        raise ValueError(f"fmt must be 'mxfp4', 'mxfp6' or 'fp8', not {fmt!r}")
     packed = packed.view(-1)
     src = layer_nbytes(spec)
     if fmt == "fp8":
@@ -194,10 +203,10 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, 
         need = fp8_packed_size(src, chunk_bytes, block)
     else:
         if block != 32:
-            raise ValueError("MXFP4 has a fixed scale block of 32 elements")
+            raise ValueError(f"{fmt.upper()} has a fixed scale block of 32 elements")
         if chunk_bytes <= 0 or chunk_bytes % 1024:
             raise ValueError("chunk_bytes must be a positive multiple of 1024")
-        need = mxfp4_packed_size(src, chunk_bytes)
+        need = (mxfp6_packed_size if fmt == "mxfp6" else mxfp4_packed_size)(src, chunk_bytes)
     if packed.numel() < need:
         raise ValueError(f"packed holds {packed.numel()} B, the layer's packed image needs {need}")
     out = {}
@@ -209,10 +218,14 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, 
 
 
 def _linear(x: torch.Tensor, w: Param) -> torch.Tensor:
-    """x @ w.T: from the packed bytes for a PackedParam, F.linear for a tensor."""
+    """x @ w.T: from the packed bytes for a PackedParam, F.linear for a tensor. MXFP6 has
+    no in-place kernel yet: such a parameter is dequantized (ops.mxfp6_unpack_range, the
+    gfx950 unpack kernel on the GPU) and multiplied with F.linear."""
     if isinstance(w, PackedParam):
         from ..ops import fp8_linear, mxfp4_linear
 
+        if w.fmt == "mxfp6":
+            return F.linear(x, w.dequantize())
         if w.fmt == "fp8":
             return fp8_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
                               block=w.block, elem_offset=w.elem_offset, out_dtype=x.dtype)
@@ -269,7 +282,7 @@ def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
 def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool) -> torch.Tensor:
     """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two MXFP4 PackedParams of
     one layer with equal shapes (on the CPU the very ops of the other route). There is no
-    fused kernel for fp8: such parameters take one ops.fp8_linear each."""
+    fused kernel for fp8 or MXFP6: such parameters take one linear each."""
     if fuse and _same_layer(wg, wu) and wg.fmt == "mxfp4" and wg.shape == wu.shape:
         from ..ops import mxfp4_swiglu
 

@@ -12,6 +12,7 @@ must never be handed a buffer smaller than its grid assumes).
     q, s = ops.fp8_pack(x)                    # OCP e4m3fn + one f32 scale per 128 values
     y = ops.fp8_unpack(q, s)                  # bf16 again
     q4, s4 = ops.mxfp4_pack(x)                # MXFP4: e2m1 pairs + one E8M0 scale per 32 values
+    q6, s6 = ops.mxfp6_pack(x)                # MXFP6: 24 bytes of e2m3 codes + one E8M0 scale per 32 values
     crc = ops.crc32c(x.view(torch.uint8), 64 << 20)   # CRC32C per 64 MiB chunk
     w = x.view(4096, 4096)                              # a bf16 [out, in] weight ...
     p = ops.mxfp4_pack_layer(x, 64 << 20)               # ... as an MXFP4-packed layer (17/64 of the bytes)
@@ -54,6 +55,13 @@ __all__ = [
     "mxfp4_unpack_range",
     "mxfp4_linear",
     "mxfp4_swiglu",
+    "mxfp6_pack",
+    "mxfp6_unpack",
+    "mxfp6_pack_layer",
+    "mxfp6_verify_unpack",
+    "mxfp6_verify_unpack_chunks",
+    "mxfp6_packed_size",
+    "mxfp6_unpack_range",
     "fp8_unpack_range",
     "fp8_linear",
 ]
@@ -370,6 +378,181 @@ def mxfp4_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, e
         # r and e - elem_offset are multiples of 32: q 16-B, the output 64-B aligned
         _core.mxfp4_unpack(base + r // 2, base + nc // 2 + r // _MX_BLOCK, take, out.data_ptr() + 2 * (e - elem_offset),
                            stream)
+        e += take
+    return out
+
+
+# ---- MXFP6 (core/mxfp6.h): e2m3 codes, 24 bytes per 32 values (value i at bits
+# [6i, 6i + 6) of its block), one E8M0 scale byte per 32 values
+
+_MX6_BLOCK_BYTES = 24
+
+
+def _on_cpu(t: torch.Tensor, name: str, dtype=None) -> bool:
+    """True for a CPU tensor (checked like _check_dev's, without device or alignment)."""
+    if t.is_cuda:
+        return False
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if dtype is not None and t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    return True
+
+
+def mxfp6_pack(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bf16 -> MXFP6 (OCP MX, e2m3): 24 bytes of 6-bit codes per 32 values (value i
+    of a block at bits [6i, 6i + 6) of its 24 bytes read as one little-endian
+    integer) and one E8M0 scale byte per 32 values (2^E, the smallest E in
+    [-126, 125] with the block's finite amax <= 7.5 * 2^E; core/mxfp6.h). Values
+    round to the nearest code, ties to the even one; +-inf saturate to
+    +-7.5 * 2^E; a block that holds a NaN is stored as scale 0xFF with zero codes.
+    Returns (q: uint8 [3 n / 4], scales: uint8 [n / 32]). CPU tensors go through
+    the host reference."""
+    cpu = _on_cpu(x, "x", torch.bfloat16)
+    if not cpu:
+        _check_dev(x, "x", torch.bfloat16)
+    n = x.numel()
+    if n % _MX_BLOCK:
+        raise ValueError(f"numel ({n}) must be a multiple of {_MX_BLOCK}")
+    if cpu:
+        qb, sb = _core.mxfp6_pack_host(x.view(torch.int16).numpy().tobytes())
+        return torch.frombuffer(bytearray(qb), dtype=torch.uint8), torch.frombuffer(bytearray(sb), dtype=torch.uint8)
+    q = torch.empty(n // _MX_BLOCK * _MX6_BLOCK_BYTES, dtype=torch.uint8, device=x.device)
+    s = torch.empty(n // _MX_BLOCK, dtype=torch.uint8, device=x.device)
+    _core.mxfp6_pack(x.data_ptr(), n, q.data_ptr(), s.data_ptr(), _stream())
+    return q, s
+
+
+def mxfp6_unpack(q: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """Inverse of `mxfp6_pack`: bf16 values code * 2^(scale - 127), exact (bf16
+    subnormals included); scale 0xFF gives NaN (0x7FC0) for the whole block.
+    `q` uint8 [3 n / 4], `scales` uint8 [n / 32] (or its ``torch.float8_e8m0fnu``
+    view). CPU tensors go through the host reference."""
+    q = _as_bytes(q, "q", None)
+    scales = _as_bytes(scales, "scales", getattr(torch, "float8_e8m0fnu", None))
+    cpu = _on_cpu(q, "q")
+    if cpu:
+        _on_cpu(scales, "scales")
+    else:
+        _check_dev(q, "q", align=8)
+        _check_dev(scales, "scales", align=1)
+    if q.device != scales.device:
+        raise ValueError("q and scales must be on the same device")
+    if q.numel() % _MX6_BLOCK_BYTES or scales.numel() != q.numel() // _MX6_BLOCK_BYTES:
+        raise ValueError("scales must hold one byte per 24 bytes of q")
+    n = scales.numel() * _MX_BLOCK
+    if cpu:
+        out = _core.mxfp6_unpack_host(q.numpy().tobytes(), scales.numpy().tobytes())
+        return torch.frombuffer(bytearray(out), dtype=torch.bfloat16) if n else torch.empty(0, dtype=torch.bfloat16)
+    y = torch.empty(n, dtype=torch.bfloat16, device=q.device)
+    _core.mxfp6_unpack(q.data_ptr(), scales.data_ptr(), n, y.data_ptr(), _stream())
+    return y
+
+
+def mxfp6_packed_size(src_bytes: int, chunk_bytes: int) -> int:
+    """Bytes of a bf16 layer of `src_bytes` in the chunked MXFP6 wire/HBM layout (25/64)."""
+    return _core.mxfp6_packed_size(src_bytes, chunk_bytes)
+
+
+def mxfp6_pack_layer(x: torch.Tensor, chunk_bytes: int) -> torch.Tensor:
+    """A whole bf16 layer into the data engine's packed layout (core/mxfp6.h): per
+    source chunk of `chunk_bytes`, [e2m3 blocks][E8M0 scales]. Returns uint8. CPU
+    tensors go through the host reference."""
+    cpu = _on_cpu(x, "x", torch.bfloat16)
+    if not cpu:
+        _check_dev(x, "x", torch.bfloat16)
+    src = _nbytes(x)
+    if chunk_bytes <= 0 or chunk_bytes % 4096 or src % (2 * _MX_BLOCK):
+        raise ValueError("chunk_bytes must be a positive multiple of 4096 and the layer a multiple of 64 B")
+    out = torch.empty(mxfp6_packed_size(src, chunk_bytes), dtype=torch.uint8, device=x.device)
+    if cpu:
+        _core.mxfp6_pack_layer_into(x.data_ptr(), src, chunk_bytes, out.data_ptr())
+    else:
+        _core.mxfp6_pack_chunks(x.data_ptr(), src, chunk_bytes, out.data_ptr(), _stream())
+    return out
+
+
+def mxfp6_verify_unpack(packed: torch.Tensor, src_bytes: int, chunk_bytes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """CRC32C of every packed chunk of an MXFP6-packed layer and the dequantized
+    bf16 layer: the CRC walk, then the unpack kernel, on the current stream (the
+    packed bytes are read twice; kernels/mxfp6.hip).
+    Returns (bf16 [src_bytes / 2], crcs int32 [chunks])."""
+    _check_dev(packed, "packed", torch.uint8)
+    if chunk_bytes <= 0 or chunk_bytes % 4096 or src_bytes <= 0 or src_bytes % (2 * _MX_BLOCK):
+        raise ValueError("bad chunk_bytes / src_bytes")
+    pbytes = mxfp6_packed_size(src_bytes, chunk_bytes)
+    if packed.numel() < pbytes:
+        raise ValueError(f"packed holds {packed.numel()} bytes, the layout needs {pbytes}")
+    pchunk = chunk_bytes // 64 * 25
+    nchunks = (pbytes + pchunk - 1) // pchunk
+    out = torch.empty(src_bytes // 2, dtype=torch.bfloat16, device=packed.device)
+    crcs = torch.empty(nchunks, dtype=torch.int32, device=packed.device)
+    ws = torch.zeros(_core.crc32c_workspace_bytes(pbytes, pchunk), dtype=torch.uint8, device=packed.device)
+    _core.mxfp6_verify_unpack_async(packed.data_ptr(), src_bytes, chunk_bytes, out.data_ptr(), crcs.data_ptr(),
+                                    ws.data_ptr(), _stream())
+    return out, crcs
+
+
+def mxfp6_verify_unpack_chunks(chunks: List[Tuple[torch.Tensor, int]]) -> Tuple[List[torch.Tensor], torch.Tensor]:
+    """The engine's batched form: independent packed chunks [(packed uint8, src_len), ...]
+    (each the core/mxfp6.h image of `src_len` bf16 bytes, up to `_core.crc32c_batch_max()`
+    of them) checked in one CRC launch and dequantized in one unpack launch.
+    Returns ([bf16 per chunk], crcs int32)."""
+    if not chunks or len(chunks) > _core.crc32c_batch_max():
+        raise ValueError(f"1 to {_core.crc32c_batch_max()} chunks per launch")
+    outs, items = [], []
+    dev = chunks[0][0].device
+    for packed, src_len in chunks:
+        _check_dev(packed, "packed", torch.uint8)
+        if packed.device != dev:
+            raise ValueError("every chunk of one launch must be on the same GPU")
+        if src_len <= 0 or src_len % (2 * _MX_BLOCK):
+            raise ValueError("src_len must be a positive multiple of 64")
+        need = src_len // 64 * 25
+        if packed.numel() < need:
+            raise ValueError(f"packed chunk holds {packed.numel()} bytes, its layout needs {need}")
+        y = torch.empty(src_len // 2, dtype=torch.bfloat16, device=dev)
+        outs.append(y)
+        items.append((packed.data_ptr(), src_len, y.data_ptr()))
+    crcs = torch.empty(len(chunks), dtype=torch.int32, device=dev)
+    ws = torch.zeros(_core.crc32c_batch_workspace_bytes(), dtype=torch.uint8, device=dev)
+    _core.mxfp6_verify_unpack_batch_async(items, crcs.data_ptr(), ws.data_ptr(), _stream())
+    return outs, crcs
+
+
+def mxfp6_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, elem_offset: int, n: int) -> torch.Tensor:
+    """Elements [elem_offset, elem_offset + n) of an MXFP6-packed layer (the chunked
+    layout of `mxfp6_pack_layer`) as bf16 [n], on `packed`'s device. Offset and
+    count are multiples of 32. GPU: the unpack kernel once per source chunk the
+    range touches, on the current stream; CPU: the host reference."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous 1-D uint8 tensor")
+    if chunk_bytes <= 0 or chunk_bytes % 1024 or src_bytes <= 0 or src_bytes % (2 * _MX_BLOCK):
+        raise ValueError("chunk_bytes must be a positive multiple of 1024 and src_bytes a positive multiple of 64")
+    need = mxfp6_packed_size(src_bytes, chunk_bytes)
+    if packed.numel() < need:
+        raise ValueError(f"packed holds {packed.numel()} bytes, the layout needs {need}")
+    if packed.is_cuda and packed.data_ptr() % 16:
+        raise ValueError("packed must be 16-byte aligned")
+    _check_range(src_bytes, elem_offset, n)
+    out = torch.empty(n, dtype=torch.bfloat16, device=packed.device)
+    if n == 0:
+        return out
+    if not packed.is_cuda:
+        _core.mxfp6_unpack_range_host(packed.data_ptr(), packed.numel(), src_bytes, chunk_bytes, elem_offset, n,
+                                      out.data_ptr())
+        return out
+    total, ce, pchunk = src_bytes // 2, chunk_bytes // 2, chunk_bytes // 64 * 25
+    e, end, stream = elem_offset, elem_offset + n, _stream()
+    while e < end:
+        c, r = divmod(e, ce)
+        nc = min(ce, total - c * ce)
+        take = min(end - e, nc - r)
+        base = packed.data_ptr() + c * pchunk
+        # r and e - elem_offset are multiples of 32: q 8-B, the output 64-B aligned
+        _core.mxfp6_unpack(base + r // _MX_BLOCK * _MX6_BLOCK_BYTES,
+                           base + nc // _MX_BLOCK * _MX6_BLOCK_BYTES + r // _MX_BLOCK, take,
+                           out.data_ptr() + 2 * (e - elem_offset), stream)
         e += take
     return out
 

@@ -167,19 +167,19 @@ class Runtime:
         self.engine_kind = engine
         self.storage_path = storage_path
         self.chunk_bytes = cfg.chunk_bytes or chunk_bytes
-        if pack not in ("none", "fp8", "mxfp4"):
+        if pack not in ("none", "fp8", "mxfp4", "mxfp6"):
             raise ValueError(f"unknown pack format {pack!r}")
-        if pack == "mxfp4":
-            # OCP MX fixes the scale block at 32 elements (core/mxfp4.h)
+        if pack in ("mxfp4", "mxfp6"):
+            # OCP MX fixes the scale block at 32 elements (core/mxfp4.h, core/mxfp6.h)
             if pack_block not in (32, 128):  # 128: the argument's default
-                raise ValueError(f"--pack mxfp4 has a fixed scale block of 32 elements, not {pack_block}")
+                raise ValueError(f"--pack {pack} has a fixed scale block of 32 elements, not {pack_block}")
             pack_block = 32
         if pack != "none" and engine not in ("rccl", "sim"):
             raise ValueError("--pack needs the planned (rccl/sim) data engine")
         if store not in ("packed", "bf16"):
             raise ValueError(f"unknown store format {store!r}")
         if store == "bf16" and pack == "none":
-            raise ValueError("--store bf16 dequantizes packed layers: it needs --pack fp8 or --pack mxfp4")
+            raise ValueError("--store bf16 dequantizes packed layers: it needs --pack fp8, --pack mxfp4 or --pack mxfp6")
         self.pack = pack
         self.store = store
         self.pack_block = pack_block
@@ -231,10 +231,10 @@ class Runtime:
             if bad or self.chunk_bytes % unit:
                 raise ValueError(f"--pack fp8 needs layer sizes and the chunk size to be multiples of {unit} B "
                                  f"(2 bytes x {pack_block}-element scale blocks); layers {sorted(bad)[:8]} are not")
-        elif pack == "mxfp4":
+        elif pack in ("mxfp4", "mxfp6"):
             bad = {l: s for l, s in self.sizes.items() if s % 64}
             if bad or self.chunk_bytes % 1024:
-                raise ValueError("--pack mxfp4 needs layer sizes that are multiples of 64 B (32 bf16 values per "
+                raise ValueError(f"--pack {pack} needs layer sizes that are multiples of 64 B (32 bf16 values per "
                                  f"scale) and a chunk size that is a multiple of 1024 B; layers {sorted(bad)[:8]} are not")
         self.epoch = 0
         self._closed = False
@@ -273,7 +273,7 @@ class Runtime:
             pcfg.chunk_bytes = self.chunk_bytes
             pcfg.verify = verify
             pcfg.poison = poison
-            pcfg.pack = {"none": 0, "fp8": 1, "mxfp4": 2}[pack]
+            pcfg.pack = {"none": 0, "fp8": 1, "mxfp4": 2, "mxfp6": 3}[pack]
             pcfg.pack_block = pack_block
             pcfg.unpack_store = store == "bf16"
             pcfg.inject_corrupt = inject_corrupt
@@ -305,7 +305,7 @@ class Runtime:
             self.engine = None  # host engines are per session (they bind to one node)
         else:
             raise ValueError(f"unknown engine {engine}")
-        # Bytes of each layer in the target tier and on the wire (packed with --pack fp8 / mxfp4),
+        # Bytes of each layer in the target tier and on the wire (packed with --pack fp8 / mxfp4 / mxfp6),
         # and the chunk grid transfers/CRCs run on.
         if self.engine is not None:
             self.slot_sizes = {l: self.engine.slot_size(s) for l, s in self.sizes.items()}
@@ -361,7 +361,7 @@ class Runtime:
     def _gen_layer(self, layer: int, size: int, seed: int, host_buf=None) -> None:
         """Generate a layer's source bytes (layer_source, or random bf16 bit
         patterns), optionally copy them to `host_buf`, put the target-tier image
-        (packed with --pack fp8 / mxfp4) into the layer's HBM slot and record its CRC
+        (packed with --pack fp8 / mxfp4 / mxfp6) into the layer's HBM slot and record its CRC
         manifest."""
         slot = self.engine.device_ptr(layer)
         ssz = self.slot_sizes[layer]
@@ -372,6 +372,8 @@ class Runtime:
                     self._fill_from_source(tmp, layer, size, seed, host_buf)
                     if self.pack == "mxfp4":
                         _core.mxfp4_pack_chunks(tmp, size, self.chunk_bytes, slot)
+                    elif self.pack == "mxfp6":
+                        _core.mxfp6_pack_chunks(tmp, size, self.chunk_bytes, slot)
                     else:
                         _core.fp8_pack_chunks(tmp, size, self.chunk_bytes, self.pack_block, slot)
                     _core.device_synchronize()
@@ -387,6 +389,8 @@ class Runtime:
                 data = _core.fp8_pack_layer_host(data, self.chunk_bytes, self.pack_block)
             elif self.pack == "mxfp4":
                 data = _core.mxfp4_pack_layer_host(data, self.chunk_bytes)
+            elif self.pack == "mxfp6":
+                data = _core.mxfp6_pack_layer_host(data, self.chunk_bytes)
             _core.sim_write(slot, data)
         self.engine.set_manifest(layer, _core.CrcManifest(self.grid, self._dev_crc(slot, ssz)))
 
@@ -558,7 +562,7 @@ class Runtime:
             raise ValueError(
                 f"node {self.node_id}: its {len(layers)} layer slots need {need / 2**30:.1f} GiB of HBM but only "
                 f"{free / 2**30:.1f} of {total / 2**30:.1f} GiB are free (keeping {self.HBM_HEADROOM >> 30} GiB "
-                f"headroom); use --pack fp8 or --pack mxfp4, or an assignment that partitions the layers")
+                f"headroom); use --pack fp8, --pack mxfp4 or --pack mxfp6, or an assignment that partitions the layers")
 
     # ------------------------------------------------------ persist / resume
     PERSIST_MANIFEST = "manifest.json"
@@ -1118,7 +1122,7 @@ class Runtime:
                 "lane_busy_ms": list(es.lane_busy_ms)}
 
     def layer_bytes(self, layer: int) -> bytes:
-        """Bytes of a layer in this rank's target tier (packed with --pack fp8 / mxfp4)."""
+        """Bytes of a layer in this rank's target tier (packed with --pack fp8 / mxfp4 / mxfp6)."""
         if self.engine is not None:
             ptr = self.engine.device_ptr(layer)
             n = self.slot_sizes[layer]
@@ -1152,6 +1156,8 @@ class Runtime:
             got = _core.host_crc32c_chunks(ptr, self.slot_sizes[layer], self.grid)
             if self.pack == "mxfp4":
                 out = _core.mxfp4_unpack_layer_host(packed, size, self.chunk_bytes)
+            elif self.pack == "mxfp6":
+                out = _core.mxfp6_unpack_layer_host(packed, size, self.chunk_bytes)
             else:
                 out = _core.fp8_unpack_layer_host(packed, size, self.chunk_bytes, self.pack_block)
         else:
@@ -1159,6 +1165,8 @@ class Runtime:
             try:
                 if self.pack == "mxfp4":
                     got = _core.mxfp4_verify_unpack(ptr, size, self.chunk_bytes, dev)
+                elif self.pack == "mxfp6":
+                    got = _core.mxfp6_verify_unpack(ptr, size, self.chunk_bytes, dev)
                 else:
                     got = _core.fp8_verify_unpack(ptr, size, self.chunk_bytes, self.pack_block, dev)
                 buf = _core.HostBuffer.malloc(size)
@@ -1176,7 +1184,7 @@ class Runtime:
         """The layer as this rank holds it in HBM, as a uint8 torch tensor.
 
         rccl engine: a zero-copy view of the layer's HBM slot (the packed image
-        with --pack fp8 / mxfp4; ``unpacked=True`` with --store bf16: the dequantized bf16
+        with --pack fp8 / mxfp4 / mxfp6; ``unpacked=True`` with --store bf16: the dequantized bf16
         image the fused verify+unpack wrote), valid until close(). The view keeps
         this Runtime alive. Other engines: a CPU copy of the same bytes."""
         import torch
@@ -1201,7 +1209,7 @@ class Runtime:
     def layer_params(self, layer: int, spec, packed: bool = False):
         """Named bf16 parameter views of a layer that holds a models/weights.py
         blob: zero-copy in HBM on the rccl engine (the dequantized image with
-        --pack fp8 / mxfp4 and --store bf16), CPU copies otherwise.
+        --pack fp8 / mxfp4 / mxfp6 and --store bf16), CPU copies otherwise.
 
         ``packed=True`` (--pack mxfp4 --store packed only): a PackedParam per name
         over layer_tensor(layer) - the packed slot itself on the rccl engine, with
@@ -1222,13 +1230,15 @@ class Runtime:
 
     def packed_layer_params(self, layer: int, spec):
         """A PackedParam per name over layer_tensor(layer), for --store packed with
-        --pack mxfp4 or --pack fp8 (the latter with this session's scale block): the
+        --pack mxfp4, --pack fp8 (with this session's scale block) or --pack mxfp6: the
         packed slot itself on the rccl engine, with no bf16 image, for decoder_forward
-        to use in place - ops.mxfp4_linear / ops.mxfp4_swiglu, or ops.fp8_linear."""
+        to use in place - ops.mxfp4_linear / ops.mxfp4_swiglu, or ops.fp8_linear. MXFP6
+        has no in-place kernel yet: its parameters are dequantized per use
+        (ops.mxfp6_unpack_range) and then multiplied."""
         from ..models.weights import unflatten_packed
 
-        if self.pack not in ("mxfp4", "fp8") or self.store != "packed":
-            raise ValueError("packed parameters need --store packed with --pack mxfp4 or --pack fp8")
+        if self.pack not in ("mxfp4", "fp8", "mxfp6") or self.store != "packed":
+            raise ValueError("packed parameters need --store packed with --pack mxfp4, --pack fp8 or --pack mxfp6")
         return unflatten_packed(self.layer_tensor(layer), spec, self.chunk_bytes, self.pack, self.pack_block)
 
     def close(self) -> None:
