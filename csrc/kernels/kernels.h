@@ -165,5 +165,20 @@ hipError_t fp8_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, 
                       const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
                       int split_k, int row_tiles_per_wave, hipStream_t s);
 
+// ---- mxfp6_linear.hip: the same product with W read in place from an
+// MXFP6-packed layer (core/mxfp6.h: 24 bytes of e2m3 codes and one E8M0 scale
+// byte per 32 elements, per source chunk; mxfp6::unpack_range_host defines
+// where an element lies). The contract is mxfp4_linear's - x, y, ldy, M, N, K,
+// elem_off (a multiple of 32), f32 accumulation on v_mfma_f32_16x16x32_bf16,
+// `split_k`, `row_tiles_per_wave`, stream order, no allocation, no workspace,
+// no atomics, equal inputs give equal bits - with `src_chunk` a positive
+// multiple of 1024 (every packed chunk, 25 bytes per 64, then starts 16-B
+// aligned), `src_bytes` a positive multiple of 64 and `packed` 16-B aligned.
+// Anything else: hipErrorInvalidValue.
+int mxfp6_linear_slices(int64_t M, int64_t N, int64_t K);
+hipError_t mxfp6_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, const uint16_t* x,
+                        int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
+                        int row_tiles_per_wave, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

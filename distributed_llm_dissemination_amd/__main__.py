@@ -331,9 +331,8 @@ def _check_weights(rt, spec, layers, my_id: int) -> None:
     seeded weights. With --pack mxfp4 --store packed the pass runs from the packed
     slot (ops.mxfp4_linear for q/k/v, o and down, ops.mxfp4_swiglu for the gated
     front half of the MLP), with no bf16 copy of the weights; with --pack fp8
-    --store packed likewise, through ops.fp8_linear. With --pack mxfp6 --store
-    packed every projection dequantizes its parameter from the slot
-    (ops.mxfp6_unpack_range) and multiplies: there is no in-place MXFP6 kernel yet."""
+    --store packed likewise, through ops.fp8_linear, and with --pack mxfp6
+    --store packed through ops.mxfp6_linear."""
     import torch
 
     from .models.weights import decoder_forward, random_layer

@@ -30,9 +30,9 @@ five weight launches: q/k/v as one ``ops.fp8_linear``, ``o_proj``, gate, up (the
 fp8 SwiGLU; ``silu(g) * u`` is plain torch) and ``down_proj``.
 
 ``--pack mxfp6 --store packed`` gives ``PackedParam``s with ``fmt="mxfp6"`` from the same
-call. There is no in-place MXFP6 kernel yet: every projection dequantizes its parameter
-from the slot (``ops.mxfp6_unpack_range``; on the GPU the merged q/k/v in one piece) and
-multiplies with ``F.linear``, so the slot stays the only resident copy of the weights.
+call, and ``decoder_forward`` runs the layer from the e2m3 blocks and E8M0 scale bytes in
+five weight launches as well: q/k/v as one ``ops.mxfp6_linear``, ``o_proj``, gate, up (no fused
+MXFP6 SwiGLU either) and ``down_proj``. Only the two norm weights are dequantized.
 
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
@@ -218,14 +218,14 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, 
 
 
 def _linear(x: torch.Tensor, w: Param) -> torch.Tensor:
-    """x @ w.T: from the packed bytes for a PackedParam, F.linear for a tensor. MXFP6 has
-    no in-place kernel yet: such a parameter is dequantized (ops.mxfp6_unpack_range, the
-    gfx950 unpack kernel on the GPU) and multiplied with F.linear."""
+    """x @ w.T: from the packed bytes for a PackedParam (ops.mxfp4_linear, ops.mxfp6_linear
+    or ops.fp8_linear by its format), F.linear for a tensor."""
     if isinstance(w, PackedParam):
-        from ..ops import fp8_linear, mxfp4_linear
+        from ..ops import fp8_linear, mxfp4_linear, mxfp6_linear
 
         if w.fmt == "mxfp6":
-            return F.linear(x, w.dequantize())
+            return mxfp6_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes,
+                                chunk_bytes=w.chunk_bytes, elem_offset=w.elem_offset, out_dtype=x.dtype)
         if w.fmt == "fp8":
             return fp8_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
                               block=w.block, elem_offset=w.elem_offset, out_dtype=x.dtype)
@@ -294,9 +294,9 @@ def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool) -> torch.Tensor:
 def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
-    packed bytes (ops.mxfp4_linear or ops.fp8_linear), a packed norm weight is
-    dequantized once. With `fuse`, MXFP4 gate and up projections run as one
-    ops.mxfp4_swiglu and, on the GPU, packed q, k and v of either format as one linear;
+    packed bytes (ops.mxfp4_linear, ops.mxfp6_linear or ops.fp8_linear), a packed norm
+    weight is dequantized once. With `fuse`, MXFP4 gate and up projections run as one
+    ops.mxfp4_swiglu and, on the GPU, packed q, k and v of any one format as one linear;
     parameters that do not allow it (a mix of tensors and PackedParams or of formats,
     other layouts) fall back per projection."""
     b, s, _ = x.shape

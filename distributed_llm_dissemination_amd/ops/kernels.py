@@ -1,8 +1,8 @@
 """PyTorch-facing wrappers of the gfx950 kernels (csrc/kernels/*.hip).
 
 Every op takes and returns CUDA (HIP) tensors (the consumers of a packed
-layer, mxfp4_unpack_range, mxfp4_linear, mxfp4_swiglu, fp8_unpack_range and
-fp8_linear, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
+layer, mxfp4_unpack_range, mxfp4_linear, mxfp4_swiglu, fp8_unpack_range,
+fp8_linear, mxfp6_unpack_range and mxfp6_linear, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
 dtypes, alignment and sizes are checked on the host before any launch (a kernel
 must never be handed a buffer smaller than its grid assumes).
 
@@ -22,6 +22,8 @@ must never be handed a buffer smaller than its grid assumes).
                          gate_offset=0, up_offset=2048 * 4096)                              # wg, wu = w[:2048], w[2048:]
     p8 = ops.fp8_pack_layer(x, 64 << 20)                # the same layer fp8-packed (33/64 of the bytes at block 128)
     y8 = ops.fp8_linear(h, p8, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20)   # h @ w.T from those bytes
+    p6 = ops.mxfp6_pack_layer(x, 64 << 20)              # the same layer MXFP6-packed (25/64 of the bytes)
+    y6 = ops.mxfp6_linear(h, p6, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20) # h @ w.T from those bytes
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
 per-chunk CRC verification of every landed chunk); here they are usable on
@@ -62,6 +64,7 @@ __all__ = [
     "mxfp6_verify_unpack_chunks",
     "mxfp6_packed_size",
     "mxfp6_unpack_range",
+    "mxfp6_linear",
     "fp8_unpack_range",
     "fp8_linear",
 ]
@@ -520,11 +523,7 @@ def mxfp6_verify_unpack_chunks(chunks: List[Tuple[torch.Tensor, int]]) -> Tuple[
     return outs, crcs
 
 
-def mxfp6_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, elem_offset: int, n: int) -> torch.Tensor:
-    """Elements [elem_offset, elem_offset + n) of an MXFP6-packed layer (the chunked
-    layout of `mxfp6_pack_layer`) as bf16 [n], on `packed`'s device. Offset and
-    count are multiples of 32. GPU: the unpack kernel once per source chunk the
-    range touches, on the current stream; CPU: the host reference."""
+def _check_mxfp6_layer(packed: torch.Tensor, src_bytes: int, chunk_bytes: int) -> int:
     if packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
         raise ValueError("packed must be a contiguous 1-D uint8 tensor")
     if chunk_bytes <= 0 or chunk_bytes % 1024 or src_bytes <= 0 or src_bytes % (2 * _MX_BLOCK):
@@ -534,6 +533,15 @@ def mxfp6_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, e
         raise ValueError(f"packed holds {packed.numel()} bytes, the layout needs {need}")
     if packed.is_cuda and packed.data_ptr() % 16:
         raise ValueError("packed must be 16-byte aligned")
+    return need
+
+
+def mxfp6_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, elem_offset: int, n: int) -> torch.Tensor:
+    """Elements [elem_offset, elem_offset + n) of an MXFP6-packed layer (the chunked
+    layout of `mxfp6_pack_layer`) as bf16 [n], on `packed`'s device. Offset and
+    count are multiples of 32. GPU: the unpack kernel once per source chunk the
+    range touches, on the current stream; CPU: the host reference."""
+    _check_mxfp6_layer(packed, src_bytes, chunk_bytes)
     _check_range(src_bytes, elem_offset, n)
     out = torch.empty(n, dtype=torch.bfloat16, device=packed.device)
     if n == 0:
@@ -735,6 +743,67 @@ def fp8_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_feat
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
     _core.fp8_linear(packed.data_ptr(), src_bytes, chunk_bytes, block, elem_offset, x2.data_ptr(), m, n, k,
                      y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
+    return y if out is not None else y.view(*lead, n)
+
+
+def mxfp6_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
+                 chunk_bytes: int, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
+    weight stored as elements [elem_offset, ...) of the MXFP6-packed layer `packed`
+    (`src_bytes` of bf16 in chunks of `chunk_bytes`, the layout of `mxfp6_pack_layer`).
+
+    GPU: one kernel on the current stream reads the 24-byte blocks of e2m3 codes and
+    their E8M0 scale bytes where they lie, dequantizes a block per instruction in
+    registers and accumulates in f32 on the bf16 MFMA; no bf16 copy of the weight is
+    made. `split_k`, `row_tiles`, `out` and the determinism are `mxfp4_linear`'s.
+    CPU: the host reference dequantizes the range, then ``F.linear`` - in f32 for an
+    f32 result, in bf16 for a bf16 one.
+    in_features and elem_offset are multiples of 32, out_features of 16, and
+    chunk_bytes of 1024 (every packed chunk then starts 16-byte aligned)."""
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"x must be {torch.bfloat16}, got {x.dtype}")
+    n, k = int(out_features), int(in_features)
+    if n <= 0 or n % 16 or k <= 0 or k % _MX_BLOCK:
+        raise ValueError("out_features must be a positive multiple of 16 and in_features of 32")
+    if x.dim() < 1 or x.shape[-1] != k or x.numel() == 0:
+        raise ValueError(f"x must be [..., {k}] with at least one row, got {tuple(x.shape)}")
+    if x.device != packed.device:
+        raise ValueError("x and packed must be on the same device")
+    if not 0 <= split_k <= 16:
+        raise ValueError("split_k must be in 0..16")
+    if row_tiles not in (0, 1, 2, 4) or (row_tiles and n // 16 % row_tiles):
+        raise ValueError("row_tiles must be 0, 1, 2 or 4 and divide out_features / 16")
+    _check_mxfp6_layer(packed, src_bytes, chunk_bytes)
+    _check_range(src_bytes, elem_offset, n * k)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, k)
+    if not x.is_cuda:
+        if out is not None:
+            raise ValueError("out is for GPU tensors")
+        w = mxfp6_unpack_range(packed, src_bytes, chunk_bytes, elem_offset, n * k).view(n, k)
+        if out_dtype == torch.float32:
+            y = torch.nn.functional.linear(x2.float(), w.float())
+        else:
+            y = torch.nn.functional.linear(x2, w)
+        return y.view(*lead, n)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() % 16:
+        x2 = x2.clone()
+    m = x2.shape[0]
+    if out is None:
+        y = torch.empty(m, n, dtype=out_dtype, device=x.device)
+    else:
+        y = out
+        if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
+            raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    _core.mxfp6_linear(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k, y.data_ptr(),
+                       y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
 
 

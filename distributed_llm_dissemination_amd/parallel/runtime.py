@@ -1232,9 +1232,8 @@ class Runtime:
         """A PackedParam per name over layer_tensor(layer), for --store packed with
         --pack mxfp4, --pack fp8 (with this session's scale block) or --pack mxfp6: the
         packed slot itself on the rccl engine, with no bf16 image, for decoder_forward
-        to use in place - ops.mxfp4_linear / ops.mxfp4_swiglu, or ops.fp8_linear. MXFP6
-        has no in-place kernel yet: its parameters are dequantized per use
-        (ops.mxfp6_unpack_range) and then multiplied."""
+        to use in place - ops.mxfp4_linear / ops.mxfp4_swiglu, ops.fp8_linear or
+        ops.mxfp6_linear."""
         from ..models.weights import unflatten_packed
 
         if self.pack not in ("mxfp4", "fp8", "mxfp6") or self.store != "packed":
