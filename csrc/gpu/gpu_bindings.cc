@@ -589,6 +589,30 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"), py::arg("split_k") = 0,
      py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("mxfp6_linear_slices", &kern::mxfp6_linear_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  // silu(x Wg^T) * (x Wu^T) from two parameters of the MXFP6-packed layer (kernels/mxfp6_swiglu.hip); stream-ordered
+  m.def("mxfp6_swiglu", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
+                           uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
+                           int split_k, int row_tiles, uint64_t stream) {
+    check(kern::mxfp6_swiglu(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, gate_off, up_off,
+                             reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                             y_bf16, split_k, row_tiles, as_stream(stream)),
+          "mxfp6_swiglu");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("gate_off"), py::arg("up_off"),
+     py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
+     py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
+  m.def("mxfp6_swiglu_slices", &kern::mxfp6_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  // the same from the fp8-packed layer (kernels/fp8_swiglu.hip); stream-ordered
+  m.def("fp8_swiglu", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t gate_off,
+                         int64_t up_off, uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy,
+                         bool y_bf16, int split_k, int row_tiles, uint64_t stream) {
+    check(kern::fp8_swiglu(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, block, gate_off, up_off,
+                           reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy, y_bf16,
+                           split_k, row_tiles, as_stream(stream)),
+          "fp8_swiglu");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block"), py::arg("gate_off"),
+     py::arg("up_off"), py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"),
+     py::arg("y_bf16"), py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
+  m.def("fp8_swiglu_slices", &kern::fp8_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
 
   // ---- RCCL path on one GPU: a one-rank communicator driven through the same
   // Backend::group / crc calls the planned engine issues. `rounds` groups of

@@ -180,5 +180,24 @@ hipError_t mxfp6_linear(const void* packed, int64_t src_bytes, int64_t src_chunk
                         int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
                         int row_tiles_per_wave, hipStream_t s);
 
+// ---- mxfp6_swiglu.hip, fp8_swiglu.hip: mxfp4_swiglu's y = silu(x * Wg^T) *
+// (x * Wu^T) from an MXFP6- or an fp8-packed layer, Wg and Wu the [N, K]
+// parameters at elements `gate_off` and `up_off` (independent multiples of 32 -
+// for fp8 too, not of the block - in any order, possibly equal). Layer
+// arguments, checks and accumulation are mxfp6_linear's / fp8_linear's, applied
+// to both parameters; with equal K slices g and u are bit for bit that
+// kernel's f32 results. Epilogue, `split_k` (0 = chosen, *_swiglu_slices; else
+// 1..16, clamped), `row_tiles_per_wave` (pairs of a gate and an up tile: 0 =
+// chosen, 1 or 2, a divisor of N / 16; 1 beyond 32 rows of x), stream order, no
+// allocation, no workspace, no atomics: as for mxfp4_swiglu.
+int mxfp6_swiglu_slices(int64_t M, int64_t N, int64_t K);
+hipError_t mxfp6_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
+                        const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
+                        int split_k, int row_tiles_per_wave, hipStream_t s);
+int fp8_swiglu_slices(int64_t M, int64_t N, int64_t K);
+hipError_t fp8_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t gate_off,
+                      int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
+                      bool y_bf16, int split_k, int row_tiles_per_wave, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

@@ -1,7 +1,8 @@
 // Device code shared by the kernels that feed v_mfma_f32_16x16x32_bf16 from an
 // MXFP4-packed layer in place (mxfp4_linear.hip, mxfp4_swiglu.hip): a lane's
 // place in the chunked layout of core/mxfp4.h, the fragment cast and the store
-// of one result. Everything here has internal linkage.
+// of one result; the last two and the swiglu epilogue also serve the fp8 and
+// MXFP6 kernels (fp8_mma.h, mxfp6_mma.h). Everything here has internal linkage.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -66,6 +67,9 @@ __device__ __forceinline__ void store_y(void* y, int64_t idx, float v) {
   if (BF16) static_cast<uint16_t*>(y)[idx] = f32_to_bf16_rne(v);
   else static_cast<float*>(y)[idx] = v;
 }
+
+// The epilogue of the *_swiglu kernels on the f32 sums g and u: silu(g) * u.
+__device__ __forceinline__ float swiglu(float g, float u) { return (g / (1.0f + expf(-g))) * u; }
 
 // The layout of a layer of `src_bytes` bf16 bytes packed in chunks of `src_chunk`.
 inline Mxfp4Layout mxfp4_layout(const void* packed, int64_t src_bytes, int64_t src_chunk) {

@@ -26,13 +26,15 @@ per projection instead.
 ``--pack fp8 --store packed`` is served the same way: ``rt.packed_layer_params(l, spec)``
 (which serves both formats) gives ``PackedParam``s with ``fmt="fp8"`` and the session's
 scale block, and ``decoder_forward`` runs the layer from the e4m3 codes and block scales in
-five weight launches: q/k/v as one ``ops.fp8_linear``, ``o_proj``, gate, up (there is no fused
-fp8 SwiGLU; ``silu(g) * u`` is plain torch) and ``down_proj``.
+five weight launches: q/k/v as one ``ops.fp8_linear``, ``o_proj``, gate, up (``silu(g) * u`` is
+plain torch) and ``down_proj``. ``decoder_forward(..., fuse_gated=True)`` opts in to the fused
+``ops.fp8_swiglu`` for gate and up: four weight launches.
 
 ``--pack mxfp6 --store packed`` gives ``PackedParam``s with ``fmt="mxfp6"`` from the same
 call, and ``decoder_forward`` runs the layer from the e2m3 blocks and E8M0 scale bytes in
-five weight launches as well: q/k/v as one ``ops.mxfp6_linear``, ``o_proj``, gate, up (no fused
-MXFP6 SwiGLU either) and ``down_proj``. Only the two norm weights are dequantized.
+five weight launches as well: q/k/v as one ``ops.mxfp6_linear``, ``o_proj``, gate, up and
+``down_proj``, or in four with ``fuse_gated=True`` (``ops.mxfp6_swiglu``). Only the two norm
+weights are dequantized.
 
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
@@ -279,26 +281,36 @@ def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
     return _linear(h, wq), _linear(h, wk), _linear(h, wv)
 
 
-def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool) -> torch.Tensor:
+def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool = False) -> torch.Tensor:
     """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two MXFP4 PackedParams of
-    one layer with equal shapes (on the CPU the very ops of the other route). There is no
-    fused kernel for fp8 or MXFP6: such parameters take one linear each."""
-    if fuse and _same_layer(wg, wu) and wg.fmt == "mxfp4" and wg.shape == wu.shape:
-        from ..ops import mxfp4_swiglu
+    one layer with equal shapes (on the CPU the very ops of the other route). Two fp8 or
+    two MXFP6 PackedParams take one ops.fp8_swiglu / ops.mxfp6_swiglu only with
+    `fuse_gated` as well (opt-in) and otherwise one linear each, as does anything else."""
+    if fuse and _same_layer(wg, wu) and wg.shape == wu.shape:
+        from ..ops import fp8_swiglu, mxfp4_swiglu, mxfp6_swiglu
 
-        return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes,
-                            gate_offset=wg.elem_offset, up_offset=wu.elem_offset, out_dtype=h.dtype)
+        kw = dict(src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes, gate_offset=wg.elem_offset,
+                  up_offset=wu.elem_offset, out_dtype=h.dtype)
+        if wg.fmt == "mxfp4":
+            return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
+        if fuse_gated and wg.fmt == "mxfp6":
+            return mxfp6_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
+        if fuse_gated and wg.fmt == "fp8":
+            return fp8_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], block=wg.block, **kw)
     return F.silu(_linear(h, wg)) * _linear(h, wu)
 
 
-def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True) -> torch.Tensor:
+def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True,
+                    fuse_gated: bool = False) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
     packed bytes (ops.mxfp4_linear, ops.mxfp6_linear or ops.fp8_linear), a packed norm
     weight is dequantized once. With `fuse`, MXFP4 gate and up projections run as one
     ops.mxfp4_swiglu and, on the GPU, packed q, k and v of any one format as one linear;
     parameters that do not allow it (a mix of tensors and PackedParams or of formats,
-    other layouts) fall back per projection."""
+    other layouts) fall back per projection. With `fuse` and `fuse_gated`, fp8 and MXFP6
+    gate and up projections of one layer run as one ops.fp8_swiglu / ops.mxfp6_swiglu as
+    well (4 weight launches on the GPU instead of 5); MXFP4 is the same either way."""
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
@@ -312,4 +324,4 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
     x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"])
     h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse), p["down_proj"])
+    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated), p["down_proj"])

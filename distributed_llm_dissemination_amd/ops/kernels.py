@@ -2,7 +2,7 @@
 
 Every op takes and returns CUDA (HIP) tensors (the consumers of a packed
 layer, mxfp4_unpack_range, mxfp4_linear, mxfp4_swiglu, fp8_unpack_range,
-fp8_linear, mxfp6_unpack_range and mxfp6_linear, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
+fp8_linear, fp8_swiglu, mxfp6_unpack_range, mxfp6_linear and mxfp6_swiglu, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
 dtypes, alignment and sizes are checked on the host before any launch (a kernel
 must never be handed a buffer smaller than its grid assumes).
 
@@ -24,6 +24,8 @@ must never be handed a buffer smaller than its grid assumes).
     y8 = ops.fp8_linear(h, p8, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20)   # h @ w.T from those bytes
     p6 = ops.mxfp6_pack_layer(x, 64 << 20)              # the same layer MXFP6-packed (25/64 of the bytes)
     y6 = ops.mxfp6_linear(h, p6, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20) # h @ w.T from those bytes
+    z6 = ops.mxfp6_swiglu(h, p6, 2048, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20, # the gated front half from
+                          gate_offset=0, up_offset=2048 * 4096)                             # those bytes (fp8_swiglu: p8)
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
 per-chunk CRC verification of every landed chunk); here they are usable on
@@ -67,6 +69,8 @@ __all__ = [
     "mxfp6_linear",
     "fp8_unpack_range",
     "fp8_linear",
+    "mxfp6_swiglu",
+    "fp8_swiglu",
 ]
 
 _FP8_BLOCKS = (32, 64, 128, 256, 512)
@@ -870,3 +874,97 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     _core.mxfp4_swiglu(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n, k,
                        y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
+
+
+def _packed_swiglu(fmt: str, x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int,
+                   src_bytes: int, chunk_bytes: int, block: int, gate_offset: int, up_offset: int,
+                   out_dtype: torch.dtype, split_k: int, row_tiles: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """`mxfp4_swiglu`'s checks and routes for the "mxfp6" and the "fp8" layer format."""
+    if out is not None:
+        out_dtype = out.dtype
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"x must be {torch.bfloat16}, got {x.dtype}")
+    n, k = int(out_features), int(in_features)
+    if n <= 0 or n % 16 or k <= 0 or k % 32:
+        raise ValueError("out_features must be a positive multiple of 16 and in_features of 32")
+    if x.dim() < 1 or x.shape[-1] != k or x.numel() == 0:
+        raise ValueError(f"x must be [..., {k}] with at least one row, got {tuple(x.shape)}")
+    if x.device != packed.device:
+        raise ValueError("x and packed must be on the same device")
+    if not 0 <= split_k <= 16:
+        raise ValueError("split_k must be in 0..16")
+    if row_tiles not in (0, 1, 2) or (row_tiles and n // 16 % row_tiles):
+        raise ValueError("row_tiles must be 0, 1 or 2 and divide out_features / 16")
+    if fmt == "fp8":
+        _check_fp8_layer(packed, src_bytes, chunk_bytes, block)
+    else:
+        _check_mxfp6_layer(packed, src_bytes, chunk_bytes)
+    _check_range(src_bytes, gate_offset, n * k)
+    _check_range(src_bytes, up_offset, n * k)
+    lead = x.shape[:-1]
+    x2 = x.reshape(-1, k)
+    if not x.is_cuda:
+        if out is not None:
+            raise ValueError("out is for GPU tensors")
+        if fmt == "fp8":
+            wg = fp8_unpack_range(packed, src_bytes, chunk_bytes, gate_offset, n * k, block).view(n, k)
+            wu = fp8_unpack_range(packed, src_bytes, chunk_bytes, up_offset, n * k, block).view(n, k)
+        else:
+            wg = mxfp6_unpack_range(packed, src_bytes, chunk_bytes, gate_offset, n * k).view(n, k)
+            wu = mxfp6_unpack_range(packed, src_bytes, chunk_bytes, up_offset, n * k).view(n, k)
+        if out_dtype == torch.float32:
+            x2, wg, wu = x2.float(), wg.float(), wu.float()
+        y = torch.nn.functional.silu(torch.nn.functional.linear(x2, wg)) * torch.nn.functional.linear(x2, wu)
+        return y.view(*lead, n)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() % 16:
+        x2 = x2.clone()
+    m = x2.shape[0]
+    if out is None:
+        y = torch.empty(m, n, dtype=out_dtype, device=x.device)
+    else:
+        y = out
+        if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
+            raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if fmt == "fp8":
+        _core.fp8_swiglu(packed.data_ptr(), src_bytes, chunk_bytes, block, gate_offset, up_offset, x2.data_ptr(), m, n,
+                         k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
+    else:
+        _core.mxfp6_swiglu(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n, k,
+                           y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
+    return y if out is not None else y.view(*lead, n)
+
+
+def mxfp6_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
+                 chunk_bytes: int, gate_offset: int, up_offset: int, out_dtype: torch.dtype = torch.bfloat16,
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``silu(x @ Wg.T) * (x @ Wu.T)``, the front half of a gated MLP, for a bf16 `x`
+    [..., in_features] and two [out_features, in_features] weights stored as elements
+    [gate_offset, ...) and [up_offset, ...) of the MXFP6-packed layer `packed` (as in
+    `mxfp6_linear`; the offsets are independent multiples of 32, in any order).
+
+    GPU: one kernel on the current stream reads x once and both weights where they
+    lie; the two products are `mxfp6_linear`'s sums (with equal `split_k` bit for
+    bit its f32 results) and stay in the MFMA accumulators, ``(g / (1 + expf(-g))) * u``
+    is evaluated in f32 and only the result is written, rounded once. `split_k`,
+    `row_tiles` (pairs of a gate and an up tile per wave: 0, 1 or 2) and `out` as in
+    `mxfp4_swiglu`.
+    CPU: the host reference dequantizes both ranges, then
+    ``F.silu(F.linear(x, wg)) * F.linear(x, wu)`` - in f32 for an f32 result, in bf16
+    (op for op what two `mxfp6_linear` calls and the torch epilogue do) for a bf16 one."""
+    return _packed_swiglu("mxfp6", x, packed, out_features, in_features, src_bytes, chunk_bytes, 32, gate_offset,
+                          up_offset, out_dtype, split_k, row_tiles, out)
+
+
+def fp8_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
+               chunk_bytes: int, gate_offset: int, up_offset: int, block: int = 128,
+               out_dtype: torch.dtype = torch.bfloat16, split_k: int = 0, row_tiles: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`mxfp6_swiglu` for the fp8-packed layer `packed` with one scale per `block` elements
+    (as in `fp8_linear`): the products are `fp8_linear`'s sums, bit for bit with equal
+    `split_k`. The offsets are multiples of 32, not of `block`."""
+    return _packed_swiglu("fp8", x, packed, out_features, in_features, src_bytes, chunk_bytes, block, gate_offset,
+                          up_offset, out_dtype, split_k, row_tiles, out)

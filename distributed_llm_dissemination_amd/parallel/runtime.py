@@ -1215,7 +1215,8 @@ class Runtime:
         over layer_tensor(layer) - the packed slot itself on the rccl engine, with
         no bf16 image - for decoder_forward to use in place: ops.mxfp4_linear per
         projection, q/k/v in one launch on the GPU, and gate and up with
-        silu(g) * u in one ops.mxfp4_swiglu."""
+        silu(g) * u in one ops.mxfp4_swiglu. fp8 and MXFP6 slots are served by
+        packed_layer_params."""
         from ..models.weights import unflatten, unflatten_packed
 
         if packed:
@@ -1233,7 +1234,8 @@ class Runtime:
         --pack mxfp4, --pack fp8 (with this session's scale block) or --pack mxfp6: the
         packed slot itself on the rccl engine, with no bf16 image, for decoder_forward
         to use in place - ops.mxfp4_linear / ops.mxfp4_swiglu, ops.fp8_linear or
-        ops.mxfp6_linear."""
+        ops.mxfp6_linear, and with decoder_forward(..., fuse_gated=True) ops.fp8_swiglu /
+        ops.mxfp6_swiglu for gate and up."""
         from ..models.weights import unflatten_packed
 
         if self.pack not in ("mxfp4", "fp8", "mxfp6") or self.store != "packed":
