@@ -565,6 +565,28 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
      py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("mxfp4_swiglu_slices", &kern::mxfp4_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  // the same two for many rows of x, one launch for any m (kernels/mxfp4_tiled.hip); stream-ordered
+  m.def("mxfp4_linear_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,
+                                 int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
+                                 uint64_t stream) {
+    check(kern::mxfp4_linear_tiled(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, elem_off,
+                                   reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                                   y_bf16, as_stream(stream)),
+          "mxfp4_linear_tiled");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"), py::arg("x"), py::arg("m"),
+     py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"), py::arg("stream") = 0);
+  m.def("mxfp4_swiglu_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off,
+                                 int64_t up_off, uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y,
+                                 int64_t ldy, bool y_bf16, uint64_t stream) {
+    check(kern::mxfp4_swiglu_tiled(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, gate_off, up_off,
+                                   reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                                   y_bf16, as_stream(stream)),
+          "mxfp4_swiglu_tiled");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("gate_off"), py::arg("up_off"),
+     py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
+     py::arg("stream") = 0);
+  // (BM, BN): rows of x and rows of W of a workgroup's output tile in the tiled kernels
+  m.def("mxfp4_tiled_tile", []() { return std::make_pair(kern::kMxfp4TiledBM, kern::kMxfp4TiledBN); });
   // W8A16 linear from the fp8-packed layer in place (kernels/fp8_linear.hip); stream-ordered
   m.def("fp8_linear", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
                          uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,

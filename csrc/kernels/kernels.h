@@ -150,6 +150,28 @@ hipError_t mxfp4_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk
                         const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
                         int split_k, int row_tiles_per_wave, hipStream_t s);
 
+// ---- mxfp4_tiled.hip: the same two results for many rows of x, each call ONE
+// launch for any M. A workgroup owns kMxfp4TiledBM rows of x by kMxfp4TiledBN
+// rows of W, stages x through LDS for its waves and dequantizes W in registers,
+// so W is read and converted once per kMxfp4TiledBM rows instead of once per
+// 64. Layer arguments, x, y, ldy, M, N, K, the offsets and every
+// hipErrorInvalidValue case are mxfp4_linear's / mxfp4_swiglu's (there is no
+// `split_k` and no `row_tiles_per_wave`); in addition ceil(M / BM) * ceil(N /
+// BN) must fit a 1-D grid. K is never split: every output element has one f32
+// accumulator (v_mfma_f32_16x16x32_bf16) that walks K in one fixed order, so
+// y[m][n] depends only on row m of x and row n of W - the same bits for any M,
+// any N and any position in the grid (batch invariance) - and g and u of the
+// gated kernel are bit for bit the tiled linear's f32 results. Nothing is read
+// outside x[0 : M K) and the parameters' blocks and scale bytes, nothing
+// written outside y[:M, :N]. Stream-ordered, no allocation, no workspace, no atomics.
+constexpr int kMxfp4TiledBM = 128, kMxfp4TiledBN = 128;
+hipError_t mxfp4_linear_tiled(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off,
+                              const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
+                              hipStream_t s);
+hipError_t mxfp4_swiglu_tiled(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off,
+                              int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
+                              bool y_bf16, hipStream_t s);
+
 // ---- fp8_linear.hip: the same product with W read in place from an fp8-packed
 // layer (core/fp8.h: e4m3 codes and one power-of-two f32 scale per `block`
 // elements, per source chunk; fp8::unpack_range_host defines where an element

@@ -219,9 +219,10 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, 
     return out
 
 
-def _linear(x: torch.Tensor, w: Param) -> torch.Tensor:
+def _linear(x: torch.Tensor, w: Param, tiled: bool = False) -> torch.Tensor:
     """x @ w.T: from the packed bytes for a PackedParam (ops.mxfp4_linear, ops.mxfp6_linear
-    or ops.fp8_linear by its format), F.linear for a tensor."""
+    or ops.fp8_linear by its format), F.linear for a tensor. `tiled`: the many-row kernel
+    for an MXFP4 PackedParam (ops.mxfp4_linear(tiled=True)); nothing else has one."""
     if isinstance(w, PackedParam):
         from ..ops import fp8_linear, mxfp4_linear, mxfp6_linear
 
@@ -231,8 +232,9 @@ def _linear(x: torch.Tensor, w: Param) -> torch.Tensor:
         if w.fmt == "fp8":
             return fp8_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
                               block=w.block, elem_offset=w.elem_offset, out_dtype=x.dtype)
+        # `tiled` is passed only when set: without it the call is what it always was
         return mxfp4_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
-                            elem_offset=w.elem_offset, out_dtype=x.dtype)
+                            elem_offset=w.elem_offset, out_dtype=x.dtype, **({"tiled": True} if tiled else {}))
     return F.linear(x, w)
 
 
@@ -266,7 +268,7 @@ def _same_layer(*ws: Param) -> bool:
                and w.fmt == ws[0].fmt and w.block == ws[0].block for w in ws[1:])
 
 
-def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
+def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool, tiled: bool = False):
     """q, k and v of h. On the GPU, three PackedParams of one layer that lie one behind
     the other with equal in_features are one [h + 2 kv, h] weight and take one launch;
     the result is split by views. On the CPU (and for anything else) one call each."""
@@ -276,32 +278,34 @@ def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool):
             and wv.elem_offset == wk.elem_offset + _numel(wk.shape)):
         nq, nk, nv = wq.shape[0], wk.shape[0], wv.shape[0]
         y = _linear(h, PackedParam(wq.packed, wq.src_bytes, wq.chunk_bytes, wq.elem_offset, (nq + nk + nv, wq.shape[1]),
-                                   wq.fmt, wq.block))
+                                   wq.fmt, wq.block), tiled)
         return y[..., :nq], y[..., nq:nq + nk], y[..., nq + nk:]
-    return _linear(h, wq), _linear(h, wk), _linear(h, wv)
+    return _linear(h, wq, tiled), _linear(h, wk, tiled), _linear(h, wv, tiled)
 
 
-def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool = False) -> torch.Tensor:
+def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool = False,
+           tiled: bool = False) -> torch.Tensor:
     """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two MXFP4 PackedParams of
     one layer with equal shapes (on the CPU the very ops of the other route). Two fp8 or
     two MXFP6 PackedParams take one ops.fp8_swiglu / ops.mxfp6_swiglu only with
-    `fuse_gated` as well (opt-in) and otherwise one linear each, as does anything else."""
+    `fuse_gated` as well (opt-in) and otherwise one linear each, as does anything else.
+    `tiled` goes to the MXFP4 calls (ops.mxfp4_swiglu(tiled=True), or `_linear`'s)."""
     if fuse and _same_layer(wg, wu) and wg.shape == wu.shape:
         from ..ops import fp8_swiglu, mxfp4_swiglu, mxfp6_swiglu
 
         kw = dict(src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes, gate_offset=wg.elem_offset,
                   up_offset=wu.elem_offset, out_dtype=h.dtype)
         if wg.fmt == "mxfp4":
-            return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
+            return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw, **({"tiled": True} if tiled else {}))
         if fuse_gated and wg.fmt == "mxfp6":
             return mxfp6_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
         if fuse_gated and wg.fmt == "fp8":
             return fp8_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], block=wg.block, **kw)
-    return F.silu(_linear(h, wg)) * _linear(h, wu)
+    return F.silu(_linear(h, wg, tiled)) * _linear(h, wu, tiled)
 
 
 def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True,
-                    fuse_gated: bool = False) -> torch.Tensor:
+                    fuse_gated: bool = False, tiled: bool = False) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
     packed bytes (ops.mxfp4_linear, ops.mxfp6_linear or ops.fp8_linear), a packed norm
@@ -310,11 +314,16 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     parameters that do not allow it (a mix of tensors and PackedParams or of formats,
     other layouts) fall back per projection. With `fuse` and `fuse_gated`, fp8 and MXFP6
     gate and up projections of one layer run as one ops.fp8_swiglu / ops.mxfp6_swiglu as
-    well (4 weight launches on the GPU instead of 5); MXFP4 is the same either way."""
+    well (4 weight launches on the GPU instead of 5); MXFP4 is the same either way.
+    `tiled` (opt-in) runs every MXFP4 projection - merged q/k/v, o_proj, gate/up and
+    down_proj - on the many-row kernels (ops.mxfp4_linear / ops.mxfp4_swiglu with
+    tiled=True): 4 weight launches for any batch * seq instead of 4 per 64 rows, each row
+    of a projection a function of that row of its input alone. It is ignored for fp8,
+    MXFP6 and plain tensors, and on the CPU it changes nothing."""
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
-    q, k, v = _qkv(h, p, fuse)
+    q, k, v = _qkv(h, p, fuse, tiled)
     q = q.view(b, s, nh, hd).transpose(1, 2)
     k = k.view(b, s, nkv, hd).transpose(1, 2)
     v = v.view(b, s, nkv, hd).transpose(1, 2)
@@ -322,6 +331,6 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     k = k.repeat_interleave(nh // nkv, dim=1)
     v = v.repeat_interleave(nh // nkv, dim=1)
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-    x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"])
+    x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"], tiled)
     h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated), p["down_proj"])
+    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled), p["down_proj"], tiled)

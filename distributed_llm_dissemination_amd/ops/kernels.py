@@ -569,9 +569,17 @@ def mxfp6_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, e
     return out
 
 
+def _check_tiled(tiled: bool, split_k: int, row_tiles: int) -> None:
+    if tiled and split_k:
+        raise ValueError("split_k must be 0 with tiled=True: the tiled kernel never splits K")
+    if tiled and row_tiles:
+        raise ValueError("row_tiles must be 0 with tiled=True: the tiled kernel has one tile shape")
+
+
 def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                  chunk_bytes: int, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
-                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
+                 tiled: bool = False) -> torch.Tensor:
     """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
     weight stored as elements [elem_offset, ...) of the MXFP4-packed layer `packed`
     (`src_bytes` of bf16 in chunks of `chunk_bytes`, the layout of `mxfp4_pack_layer`).
@@ -585,7 +593,13 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     f32 result, in bf16 (what a plain bf16 weight gets) for a bf16 one.
     in_features and elem_offset are multiples of 32, out_features of 16.
     `out` (GPU only): a [rows, out_features] f32 or bf16 tensor to write, unit
-    stride along its rows and any row stride; its dtype replaces `out_dtype`."""
+    stride along its rows and any row stride; its dtype replaces `out_dtype`.
+    `tiled` (GPU; the CPU route is the same either way): the kernel for many rows
+    (mxfp4_tiled.hip) - one launch for any number of rows, x shared through LDS, W
+    read once per `_core.mxfp4_tiled_tile()[0]` rows instead of once per 64. K is
+    never split there, so a row of the result depends on that row of x alone (the
+    same bits in any batch); `split_k` and `row_tiles` must stay 0."""
+    _check_tiled(tiled, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -627,6 +641,10 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if tiled:
+        _core.mxfp4_linear_tiled(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k,
+                                 y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+        return y if out is not None else y.view(*lead, n)
     _core.mxfp4_linear(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k, y.data_ptr(),
                        y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
@@ -813,7 +831,8 @@ def mxfp6_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
 
 def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                  chunk_bytes: int, gate_offset: int, up_offset: int, out_dtype: torch.dtype = torch.bfloat16,
-                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
+                 tiled: bool = False) -> torch.Tensor:
     """``silu(x @ Wg.T) * (x @ Wu.T)``, the front half of a gated MLP, for a bf16 `x`
     [..., in_features] and two [out_features, in_features] weights stored as elements
     [gate_offset, ...) and [up_offset, ...) of the MXFP4-packed layer `packed` (as in
@@ -828,7 +847,9 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     CPU: the host reference dequantizes both ranges, then
     ``F.silu(F.linear(x, wg)) * F.linear(x, wu)`` - in f32 for an f32 result, in bf16
     (what plain bf16 weights get, op for op) for a bf16 one.
-    `out` (GPU only) as in `mxfp4_linear`."""
+    `out` (GPU only) as in `mxfp4_linear`. `tiled` as in `mxfp4_linear`: the gated
+    kernel for many rows, whose g and u are bit for bit the tiled linear's f32 results."""
+    _check_tiled(tiled, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -871,6 +892,10 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if tiled:
+        _core.mxfp4_swiglu_tiled(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n,
+                                 k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+        return y if out is not None else y.view(*lead, n)
     _core.mxfp4_swiglu(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n, k,
                        y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
