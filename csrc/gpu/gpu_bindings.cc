@@ -635,6 +635,50 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("up_off"), py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"),
      py::arg("y_bf16"), py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("fp8_swiglu_slices", &kern::fp8_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  // the MXFP6 and fp8 pairs for many rows of x, one launch for any m (kernels/mxfp6_tiled.hip,
+  // kernels/fp8_tiled.hip); stream-ordered
+  m.def("mxfp6_linear_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,
+                                 int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
+                                 uint64_t stream) {
+    check(kern::mxfp6_linear_tiled(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, elem_off,
+                                   reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                                   y_bf16, as_stream(stream)),
+          "mxfp6_linear_tiled");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"), py::arg("x"), py::arg("m"),
+     py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"), py::arg("stream") = 0);
+  m.def("mxfp6_swiglu_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off,
+                                 int64_t up_off, uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y,
+                                 int64_t ldy, bool y_bf16, uint64_t stream) {
+    check(kern::mxfp6_swiglu_tiled(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, gate_off, up_off,
+                                   reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                                   y_bf16, as_stream(stream)),
+          "mxfp6_swiglu_tiled");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("gate_off"), py::arg("up_off"),
+     py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
+     py::arg("stream") = 0);
+  m.def("fp8_linear_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
+                               uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
+                               uint64_t stream) {
+    check(kern::fp8_linear_tiled(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, block, elem_off,
+                                 reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                                 y_bf16, as_stream(stream)),
+          "fp8_linear_tiled");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block"), py::arg("elem_off"),
+     py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
+     py::arg("stream") = 0);
+  m.def("fp8_swiglu_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t gate_off,
+                               int64_t up_off, uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y,
+                               int64_t ldy, bool y_bf16, uint64_t stream) {
+    check(kern::fp8_swiglu_tiled(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, block, gate_off, up_off,
+                                 reinterpret_cast<const uint16_t*>(x), m_rows, n, k, reinterpret_cast<void*>(y), ldy,
+                                 y_bf16, as_stream(stream)),
+          "fp8_swiglu_tiled");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block"), py::arg("gate_off"),
+     py::arg("up_off"), py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"),
+     py::arg("y_bf16"), py::arg("stream") = 0);
+  // (BM, BN) of those kernels, per format
+  m.def("mxfp6_tiled_tile", []() { return std::make_pair(kern::kMxfp6TiledBM, kern::kMxfp6TiledBN); });
+  m.def("fp8_tiled_tile", []() { return std::make_pair(kern::kFp8TiledBM, kern::kFp8TiledBN); });
 
   // ---- RCCL path on one GPU: a one-rank communicator driven through the same
   // Backend::group / crc calls the planned engine issues. `rounds` groups of

@@ -221,5 +221,34 @@ hipError_t fp8_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, 
                       int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
                       bool y_bf16, int split_k, int row_tiles_per_wave, hipStream_t s);
 
+// ---- mxfp6_tiled.hip, fp8_tiled.hip: mxfp4_tiled.hip's two kernels for many
+// rows of x from an MXFP6- or an fp8-packed layer, each call ONE launch for any
+// M: a workgroup owns BM rows of x by BN rows of W, stages x through LDS for its
+// waves and dequantizes W in registers, so W is read and converted once per BM
+// rows instead of once per 64. Layer arguments, x, y, ldy, M, N, K, `block`, the
+// offsets and every hipErrorInvalidValue case are those of mxfp6_linear /
+// mxfp6_swiglu / fp8_linear / fp8_swiglu (there is no `split_k` and no
+// `row_tiles_per_wave`); in addition ceil(M / BM) * ceil(N / BN) (gated: BN / 2)
+// must fit a 1-D grid. K is never split: every output element has one f32
+// accumulator that walks K in the decode kernel's order, so the f32 results are
+// bit for bit those of the decode kernel with split_k = 1, y[m][n] depends only
+// on row m of x and row n of W (batch invariance), and g and u of the gated
+// kernels are the tiled linear's f32 bits. Nothing is read outside x[0 : M K)
+// and the parameters' codes and scales, nothing written outside y[:M, :N].
+// Stream-ordered, no allocation, no workspace, no atomics.
+constexpr int kMxfp6TiledBM = 128, kMxfp6TiledBN = 128, kFp8TiledBM = 128, kFp8TiledBN = 128;
+hipError_t mxfp6_linear_tiled(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off,
+                              const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
+                              hipStream_t s);
+hipError_t mxfp6_swiglu_tiled(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off,
+                              int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
+                              bool y_bf16, hipStream_t s);
+hipError_t fp8_linear_tiled(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
+                            const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
+                            hipStream_t s);
+hipError_t fp8_swiglu_tiled(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t gate_off,
+                            int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
+                            bool y_bf16, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

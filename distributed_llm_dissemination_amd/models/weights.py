@@ -36,6 +36,12 @@ five weight launches as well: q/k/v as one ``ops.mxfp6_linear``, ``o_proj``, gat
 ``down_proj``, or in four with ``fuse_gated=True`` (``ops.mxfp6_swiglu``). Only the two norm
 weights are dequantized.
 
+Those launch counts hold per 64 rows of input: the kernels above are decode kernels. With
+``decoder_forward(..., tiled=True)`` (opt-in) every packed projection, in any of the three
+formats, runs on its format's many-row kernel instead (``tiled=True`` of the same op): four
+weight launches for any batch * seq (fp8 and MXFP6: with ``fuse_gated=True``, else five), each
+row of a projection a function of that row of its input alone.
+
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
 on received weights against the originals.
@@ -222,19 +228,20 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, 
 def _linear(x: torch.Tensor, w: Param, tiled: bool = False) -> torch.Tensor:
     """x @ w.T: from the packed bytes for a PackedParam (ops.mxfp4_linear, ops.mxfp6_linear
     or ops.fp8_linear by its format), F.linear for a tensor. `tiled`: the many-row kernel
-    for an MXFP4 PackedParam (ops.mxfp4_linear(tiled=True)); nothing else has one."""
+    of a PackedParam's format (tiled=True of the same op); a tensor has none."""
     if isinstance(w, PackedParam):
         from ..ops import fp8_linear, mxfp4_linear, mxfp6_linear
 
+        # `tiled` is passed only when set: without it the call is what it always was
+        kw = {"tiled": True} if tiled else {}
         if w.fmt == "mxfp6":
             return mxfp6_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes,
-                                chunk_bytes=w.chunk_bytes, elem_offset=w.elem_offset, out_dtype=x.dtype)
+                                chunk_bytes=w.chunk_bytes, elem_offset=w.elem_offset, out_dtype=x.dtype, **kw)
         if w.fmt == "fp8":
             return fp8_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
-                              block=w.block, elem_offset=w.elem_offset, out_dtype=x.dtype)
-        # `tiled` is passed only when set: without it the call is what it always was
+                              block=w.block, elem_offset=w.elem_offset, out_dtype=x.dtype, **kw)
         return mxfp4_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes, chunk_bytes=w.chunk_bytes,
-                            elem_offset=w.elem_offset, out_dtype=x.dtype, **({"tiled": True} if tiled else {}))
+                            elem_offset=w.elem_offset, out_dtype=x.dtype, **kw)
     return F.linear(x, w)
 
 
@@ -289,14 +296,15 @@ def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool =
     one layer with equal shapes (on the CPU the very ops of the other route). Two fp8 or
     two MXFP6 PackedParams take one ops.fp8_swiglu / ops.mxfp6_swiglu only with
     `fuse_gated` as well (opt-in) and otherwise one linear each, as does anything else.
-    `tiled` goes to the MXFP4 calls (ops.mxfp4_swiglu(tiled=True), or `_linear`'s)."""
+    `tiled` goes to whichever call is made: the fused op's tiled=True, or `_linear`'s - two
+    tiled linears and the torch epilogue for fp8 and MXFP6 without `fuse_gated`."""
     if fuse and _same_layer(wg, wu) and wg.shape == wu.shape:
         from ..ops import fp8_swiglu, mxfp4_swiglu, mxfp6_swiglu
 
         kw = dict(src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes, gate_offset=wg.elem_offset,
-                  up_offset=wu.elem_offset, out_dtype=h.dtype)
+                  up_offset=wu.elem_offset, out_dtype=h.dtype, **({"tiled": True} if tiled else {}))
         if wg.fmt == "mxfp4":
-            return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw, **({"tiled": True} if tiled else {}))
+            return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
         if fuse_gated and wg.fmt == "mxfp6":
             return mxfp6_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
         if fuse_gated and wg.fmt == "fp8":
@@ -315,11 +323,13 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     other layouts) fall back per projection. With `fuse` and `fuse_gated`, fp8 and MXFP6
     gate and up projections of one layer run as one ops.fp8_swiglu / ops.mxfp6_swiglu as
     well (4 weight launches on the GPU instead of 5); MXFP4 is the same either way.
-    `tiled` (opt-in) runs every MXFP4 projection - merged q/k/v, o_proj, gate/up and
-    down_proj - on the many-row kernels (ops.mxfp4_linear / ops.mxfp4_swiglu with
-    tiled=True): 4 weight launches for any batch * seq instead of 4 per 64 rows, each row
-    of a projection a function of that row of its input alone. It is ignored for fp8,
-    MXFP6 and plain tensors, and on the CPU it changes nothing."""
+    `tiled` (opt-in) runs every packed projection - merged q/k/v, o_proj, gate/up and
+    down_proj, in any of the three formats - on the many-row kernels (the format's
+    *_linear / *_swiglu op with tiled=True): for MXFP4, and for fp8 and MXFP6 with
+    `fuse_gated`, 4 weight launches for any batch * seq instead of 4 per 64 rows (fp8
+    and MXFP6 without `fuse_gated`: 5, gate and up as two tiled linears), each row of a
+    projection a function of that row of its input alone. It is ignored for plain
+    tensors, and on the CPU it changes nothing."""
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)

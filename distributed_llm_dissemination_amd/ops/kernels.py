@@ -708,7 +708,8 @@ def fp8_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, ele
 
 def fp8_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                chunk_bytes: int, block: int = 128, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
-               split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
+               tiled: bool = False) -> torch.Tensor:
     """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
     weight stored as elements [elem_offset, ...) of the fp8-packed layer `packed`
     (`src_bytes` of bf16 in chunks of `chunk_bytes` with one scale per `block` elements,
@@ -721,7 +722,11 @@ def fp8_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_feat
     then ``F.linear`` - in f32 for an f32 result, in bf16 for a bf16 one.
     in_features and elem_offset are multiples of 32, out_features of 16, and
     chunk_bytes of 8 * block (every packed chunk then starts 16-byte aligned; the
-    engine's chunk sizes do)."""
+    engine's chunk sizes do).
+    `tiled` as in `mxfp4_linear`: the kernel for many rows (fp8_tiled.hip), one launch
+    for any number of rows, W read once per `_core.fp8_tiled_tile()[0]` rows. Its f32
+    result is bit for bit the untiled kernel's with ``split_k=1``."""
+    _check_tiled(tiled, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -763,6 +768,10 @@ def fp8_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_feat
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if tiled:
+        _core.fp8_linear_tiled(packed.data_ptr(), src_bytes, chunk_bytes, block, elem_offset, x2.data_ptr(), m, n, k,
+                               y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+        return y if out is not None else y.view(*lead, n)
     _core.fp8_linear(packed.data_ptr(), src_bytes, chunk_bytes, block, elem_offset, x2.data_ptr(), m, n, k,
                      y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
@@ -770,7 +779,8 @@ def fp8_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_feat
 
 def mxfp6_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                  chunk_bytes: int, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
-                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
+                 tiled: bool = False) -> torch.Tensor:
     """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
     weight stored as elements [elem_offset, ...) of the MXFP6-packed layer `packed`
     (`src_bytes` of bf16 in chunks of `chunk_bytes`, the layout of `mxfp6_pack_layer`).
@@ -782,7 +792,11 @@ def mxfp6_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     CPU: the host reference dequantizes the range, then ``F.linear`` - in f32 for an
     f32 result, in bf16 for a bf16 one.
     in_features and elem_offset are multiples of 32, out_features of 16, and
-    chunk_bytes of 1024 (every packed chunk then starts 16-byte aligned)."""
+    chunk_bytes of 1024 (every packed chunk then starts 16-byte aligned).
+    `tiled` as in `mxfp4_linear`: the kernel for many rows (mxfp6_tiled.hip), one launch
+    for any number of rows, W read once per `_core.mxfp6_tiled_tile()[0]` rows. Its f32
+    result is bit for bit the untiled kernel's with ``split_k=1``."""
+    _check_tiled(tiled, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -824,6 +838,10 @@ def mxfp6_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if tiled:
+        _core.mxfp6_linear_tiled(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k,
+                                 y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+        return y if out is not None else y.view(*lead, n)
     _core.mxfp6_linear(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k, y.data_ptr(),
                        y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     return y if out is not None else y.view(*lead, n)
@@ -903,8 +921,10 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
 
 def _packed_swiglu(fmt: str, x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int,
                    src_bytes: int, chunk_bytes: int, block: int, gate_offset: int, up_offset: int,
-                   out_dtype: torch.dtype, split_k: int, row_tiles: int, out: Optional[torch.Tensor]) -> torch.Tensor:
+                   out_dtype: torch.dtype, split_k: int, row_tiles: int, out: Optional[torch.Tensor],
+                   tiled: bool = False) -> torch.Tensor:
     """`mxfp4_swiglu`'s checks and routes for the "mxfp6" and the "fp8" layer format."""
+    _check_tiled(tiled, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -954,7 +974,13 @@ def _packed_swiglu(fmt: str, x: torch.Tensor, packed: torch.Tensor, out_features
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
-    if fmt == "fp8":
+    if tiled and fmt == "fp8":
+        _core.fp8_swiglu_tiled(packed.data_ptr(), src_bytes, chunk_bytes, block, gate_offset, up_offset, x2.data_ptr(),
+                               m, n, k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+    elif tiled:
+        _core.mxfp6_swiglu_tiled(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n,
+                                 k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+    elif fmt == "fp8":
         _core.fp8_swiglu(packed.data_ptr(), src_bytes, chunk_bytes, block, gate_offset, up_offset, x2.data_ptr(), m, n,
                          k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, split_k, row_tiles, _stream())
     else:
@@ -965,7 +991,8 @@ def _packed_swiglu(fmt: str, x: torch.Tensor, packed: torch.Tensor, out_features
 
 def mxfp6_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                  chunk_bytes: int, gate_offset: int, up_offset: int, out_dtype: torch.dtype = torch.bfloat16,
-                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
+                 tiled: bool = False) -> torch.Tensor:
     """``silu(x @ Wg.T) * (x @ Wu.T)``, the front half of a gated MLP, for a bf16 `x`
     [..., in_features] and two [out_features, in_features] weights stored as elements
     [gate_offset, ...) and [up_offset, ...) of the MXFP6-packed layer `packed` (as in
@@ -979,17 +1006,20 @@ def mxfp6_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     `mxfp4_swiglu`.
     CPU: the host reference dequantizes both ranges, then
     ``F.silu(F.linear(x, wg)) * F.linear(x, wu)`` - in f32 for an f32 result, in bf16
-    (op for op what two `mxfp6_linear` calls and the torch epilogue do) for a bf16 one."""
+    (op for op what two `mxfp6_linear` calls and the torch epilogue do) for a bf16 one.
+    `tiled` as in `mxfp6_linear`: the gated kernel for many rows, whose g and u are bit
+    for bit the tiled linear's f32 results."""
     return _packed_swiglu("mxfp6", x, packed, out_features, in_features, src_bytes, chunk_bytes, 32, gate_offset,
-                          up_offset, out_dtype, split_k, row_tiles, out)
+                          up_offset, out_dtype, split_k, row_tiles, out, tiled)
 
 
 def fp8_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                chunk_bytes: int, gate_offset: int, up_offset: int, block: int = 128,
                out_dtype: torch.dtype = torch.bfloat16, split_k: int = 0, row_tiles: int = 0,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out: Optional[torch.Tensor] = None, tiled: bool = False) -> torch.Tensor:
     """`mxfp6_swiglu` for the fp8-packed layer `packed` with one scale per `block` elements
     (as in `fp8_linear`): the products are `fp8_linear`'s sums, bit for bit with equal
-    `split_k`. The offsets are multiples of 32, not of `block`."""
+    `split_k`. The offsets are multiples of 32, not of `block`. `tiled`: fp8_tiled.hip's
+    gated kernel."""
     return _packed_swiglu("fp8", x, packed, out_features, in_features, src_bytes, chunk_bytes, block, gate_offset,
-                          up_offset, out_dtype, split_k, row_tiles, out)
+                          up_offset, out_dtype, split_k, row_tiles, out, tiled)
