@@ -359,7 +359,7 @@ def mxfp4_overflow(m, n, k, zeros=False, seed=0):
 FP8_TOP_E, FP8_COOL_E = 120, 96
 
 
-def fp8_overflow(m, n, k, block, seed=0):
+def fp8_overflow(m, n, k, block, seed=0, layer=None, other=-1):
     """fp8 at E = 120, where the weights reach the bf16 maximum (magnitude byte 0x77 = 240, core/fp8.h
     sat_limit; 0x78..0x7E stay out). A few "hot" weight rows lie in blocks of scale 2^120 with
     magnitudes 16..240; every other block has scale 2^96 and magnitudes 0, 1..15; what a hot block
@@ -370,8 +370,12 @@ def fp8_overflow(m, n, k, block, seed=0):
     Two "warm" rows tell finite weights at E = 120 from inf: they lie in blocks of scale 2^120 too and
     hold 0 except 6.5 and 8 (one in the main loop where K has one, one in the K tail) resp. a single
     112 at a position where every row of x holds 1. Their sums, (14.5 .. 116) * 2^120 and 112 * 2^120,
-    lie in [2^123, 2^127) and are exact (multiples of 2^117)."""
-    off, chunk, total = _fp8_layer(n, k, block)
+    lie in [2^123, 2^127) and are exact (multiples of 2^117).
+    `layer` = (off, chunk, total) replaces the default layout; `other` >= 0 is a second [n, k]
+    parameter of that layer, at least one scale block away, which gets cool codes of one sign per row
+    like the cool rows here (extra["wo"], extra["other"]: its weights and x W^T, exact as the kept
+    columns are)."""
+    off, chunk, total = _fp8_layer(n, k, block) if layer is None else layer
     rng = np.random.default_rng(21 + seed + n + k + block)
     e = np.arange(total, dtype=np.int64)
     ci, si = fp8_index(total, chunk, block, e)
@@ -388,6 +392,10 @@ def fp8_overflow(m, n, k, block, seed=0):
     for r, p, code in [(warm_rows[0], pa, 0x4D), (warm_rows[0], pb, 0x50), (warm_rows[1], pc, 0x6E)]:  # 6.5, 8, 112
         mag[off + r * k + p] = code
     sign = np.where(row >= 0, (row % 2) * 0x80, rng.integers(0, 2, total) * 0x80)
+    if other >= 0:
+        in_other = (e >= other) & (e < other + n * k)
+        assert not (hot_elem & in_other).any()
+        sign = np.where(in_other, ((e - other) // k % 2) * 0x80, sign)
     img = np.zeros(int(_core.fp8_packed_size(2 * total, chunk, block)), dtype=np.uint8)
     img[ci] = (mag | sign).astype(np.uint8)
     scales = np.ldexp(1.0, np.where(hot_elem[::block], FP8_TOP_E, FP8_COOL_E)).astype(np.float32)
@@ -406,6 +414,13 @@ def fp8_overflow(m, n, k, block, seed=0):
     assert (warm >= 2.0 ** 123).all() and (warm < 2.0 ** 127).all()
     assert (np.abs(c.wf[warm_rows]).max(1) >= 2.0 ** 123).all()
     c.extra.update(rows=hot_rows, keep=keep, warm=warm_rows)
+    if other >= 0:
+        wo = f8.ref_weight(img, total, chunk, block, other, n, k)
+        c.extra.update(wo=wo, other=xf @ wo.T)
+        cool = img.copy()  # the clean image: every scale 2^96, so the hot and warm rows stay far below 2^127
+        cool_scales = np.full(len(scales), 2.0 ** FP8_COOL_E, np.float32)
+        cool[si[::block, None] + np.arange(4)] = cool_scales.view(np.uint8).reshape(-1, 4)
+        c.extra.update(clean_img=cool)
     return c
 
 
@@ -419,10 +434,10 @@ def _bad_positions(k):
     return (5, tail0 + 1, k - 2) if nsteps == 0 else (37, 128 * (nsteps - 1) + 70, tail0 + 9)
 
 
-def nonfinite_x(x, xf, with_nan=True):
-    """(x, xf) with a NaN (with_nan), a +inf and a -inf in row BAD_ROW[m]."""
+def nonfinite_x(x, xf, with_nan=True, row=None):
+    """(x, xf) with a NaN (with_nan), a +inf and a -inf in row `row` (BAD_ROW[m] unless given)."""
     m, k = xf.shape
-    r = BAD_ROW[m]
+    r = BAD_ROW[m] if row is None else row
     bits = mx.bf16_tensor_bits(x).reshape(m, k).copy()
     pn, pp, pm = _bad_positions(k)
     if with_nan:
@@ -431,9 +446,9 @@ def nonfinite_x(x, xf, with_nan=True):
     return bits_x(bits)
 
 
-def bad_row_expectation(xf_bad, wf, want_clean):
+def bad_row_expectation(xf_bad, wf, want_clean, row=None):
     """The expectation with the bad row summed element by element (inf * 0 and inf - inf are NaN)."""
-    r = BAD_ROW[xf_bad.shape[0]]
+    r = BAD_ROW[xf_bad.shape[0]] if row is None else row
     want = want_clean.copy()
     with np.errstate(invalid="ignore"):
         want[r] = (xf_bad[r][None, :] * wf).sum(1)
@@ -441,9 +456,10 @@ def bad_row_expectation(xf_bad, wf, want_clean):
     return want
 
 
-def nonfinite_activations(fmt, n, k, m, block=128, seed=0):
-    """A clean exact case (integers in [-8, 8], ordinary weights) of M = 5, 17 or 65 rows;
-    extra["bad"] = {with_nan: (x, xf, want)} puts the non-finite values into one row of x."""
+def nonfinite_activations(fmt, n, k, m, block=128, seed=0, row=None):
+    """A clean exact case (integers in [-8, 8], ordinary weights) of M = 5, 17 or 65 rows (any M with
+    `row` given); extra["bad"] = {with_nan: (x, xf, want)} puts the non-finite values into one row of x."""
+    row = BAD_ROW[m] if row is None else row
     x, xf = mx.int_x(m, k, 41 + seed + m)
     if fmt == "fp8":
         off, chunk, total = _fp8_layer(n, k, block)
@@ -455,10 +471,10 @@ def nonfinite_activations(fmt, n, k, m, block=128, seed=0):
         c = _linear_case(fmt, img, total, chunk, 32, off, n, k, x, xf, 1.0, 2.0 ** -2)
     bad = {}
     for with_nan in (True, False):
-        xb, xbf = nonfinite_x(x, xf, with_nan)
-        bad[with_nan] = (xb, xbf, bad_row_expectation(xbf, c.wf, c.want))
-    assert np.isnan(bad[True][2][BAD_ROW[m]]).all()
-    c.extra.update(bad=bad, row=BAD_ROW[m], keep=[i for i in range(m) if i != BAD_ROW[m]])
+        xb, xbf = nonfinite_x(x, xf, with_nan, row)
+        bad[with_nan] = (xb, xbf, bad_row_expectation(xbf, c.wf, c.want, row))
+    assert np.isnan(bad[True][2][row]).all()
+    c.extra.update(bad=bad, row=row, keep=[i for i in range(m) if i != row])
     return c
 
 
@@ -473,14 +489,20 @@ def swiglu_clean(m, n, k, seed=0, chunk=1024):
     return SwigluCase(img, total, chunk, gate, up, n, k, x, xf, wg, wu, xf @ wg.T, xf @ wu.T, 1.0, 2.0 ** -2, 2.0 ** -2)
 
 
-def swiglu_nonfinite(n, k, m, seed=0):
+def swiglu_nonfinite(n, k, m, seed=0, row=None):
     """swiglu_clean with extra["bad"] = {with_nan: (x, g, u)}: the non-finite values in one row of x."""
-    c = swiglu_clean(m, n, k, seed)
+    return add_bad_rows(swiglu_clean(m, n, k, seed), row)
+
+
+def add_bad_rows(c, row=None):
+    """extra["bad"] = {with_nan: (x, g, u)} for a clean gated case (BAD_ROW[m] unless `row` is given)."""
+    m = c.x.shape[0]
+    row = BAD_ROW[m] if row is None else row
     bad = {}
     for with_nan in (True, False):
-        xb, xbf = nonfinite_x(c.x, c.xf, with_nan)
-        bad[with_nan] = (xb, bad_row_expectation(xbf, c.wg, c.g), bad_row_expectation(xbf, c.wu, c.u))
-    c.extra.update(bad=bad, row=BAD_ROW[m], keep=[i for i in range(m) if i != BAD_ROW[m]])
+        xb, xbf = nonfinite_x(c.x, c.xf, with_nan, row)
+        bad[with_nan] = (xb, bad_row_expectation(xbf, c.wg, c.g, row), bad_row_expectation(xbf, c.wu, c.u, row))
+    c.extra.update(bad=bad, row=row, keep=[i for i in range(m) if i != row])
     return c
 
 
@@ -523,6 +545,7 @@ class FarCase:
     up_s: int = -1        # swiglu: the up parameter in S (the gate is at off_s)
     wu: np.ndarray = None
     up_bits: np.ndarray = None
+    chunks: int = 3       # full chunks of S
 
     def place(self, device):
         """The packed buffer on `device`: uninitialised below S."""
@@ -536,9 +559,11 @@ def far_pchunk(fmt, block):
     return ce + ce // block * 4 if fmt == "fp8" else FAR_CHUNK // 4 + FAR_CHUNK // 64
 
 
-def far_case(fmt, c0, off_s, m=5, block=128, seed=0, up_s=-1, n=48):
+def far_case(fmt, c0, off_s, m=5, block=128, seed=0, up_s=-1, n=48, chunks=3):
+    """`chunks`: the full chunks of S, 3 unless a parameter of more rows (BN + 16 of a tiled kernel)
+    or a gate / up pair behind a crossing has to fit."""
     ce = FAR_CHUNK // 2
-    total_s = 3 * ce + 32 * 144  # the tail chunk holds 4608 elements (whole blocks of 128)
+    total_s = chunks * ce + 32 * 144  # the tail chunk holds 4608 elements (whole blocks of 128 and of 512)
     k = FAR_K
     assert off_s % 32 == 0 and max(off_s, up_s) + n * k <= total_s
     x, xf = mx.int_x(m, k, 61 + seed + m)
@@ -564,6 +589,7 @@ def far_case(fmt, c0, off_s, m=5, block=128, seed=0, up_s=-1, n=48):
     if up_s >= 0:
         c.up_s, c.up_bits = up_s, layer[up_s: up_s + n * k]
         c.wu = mx.bits_to_f64(c.up_bits).reshape(n, k)
+    c.chunks = chunks
     return c
 
 
@@ -576,6 +602,9 @@ def far_linear(c, buf, **kw):
 
 
 def far_swiglu(c, buf, **kw):
+    if c.fmt == "fp8":
+        return ops.fp8_swiglu(c.x.to(buf.device), buf, c.n, FAR_K, src_bytes=c.src_bytes, chunk_bytes=FAR_CHUNK,
+                              block=c.block, gate_offset=c.elem_offset, up_offset=c.elem_offset - c.off_s + c.up_s, **kw)
     return ops.mxfp4_swiglu(c.x.to(buf.device), buf, c.n, FAR_K, src_bytes=c.src_bytes, chunk_bytes=FAR_CHUNK,
                             gate_offset=c.elem_offset, up_offset=c.elem_offset - c.off_s + c.up_s, **kw)
 

@@ -123,6 +123,21 @@ def overflow(m, n, k, zeros=False, seed=0):
     clean = m6.handmade_image(total, chunk, 11 + seed + n + k)
     x, xf = scaled_ints(m, k, 13 + seed + m, 0, 0 if zeros else 1, 8)
     img = clean.copy()
+    rows = poison(img, total, chunk, off, n, k, seed)
+    c = _case(img, total, chunk, off, n, k, x, xf, 1.0, 2.0 ** -4)
+    cl = _case(clean, total, chunk, off, n, k, x, xf, 1.0, 2.0 ** -4)
+    keep = check_poisoned(c.wf, cl.wf, rows)
+    with np.errstate(invalid="ignore"):
+        for r in rows:
+            c.want[:, r] = (xf * c.wf[r][None, :]).sum(1)
+    assert not np.isfinite(c.want[:, rows]).any() and np.array_equal(c.want[:, keep], cl.want[:, keep])
+    c.extra.update(clean=cl, rows=rows, keep=keep)
+    return c
+
+
+def poison(img, total, chunk, off, n, k, seed=0):
+    """Writes the blocks of _poison_rows into the [n, k] parameter at element `off` of `img`;
+    returns the poisoned weight rows."""
     rng = np.random.default_rng(seed + 5)
     rows = []
     for r, blocks in _poison_rows(n, k):
@@ -137,41 +152,35 @@ def overflow(m, n, k, zeros=False, seed=0):
             qi, si = mxfp6_index(total, chunk, off + r * k + 32 * b)
             img[qi: qi + 24] = codes_to_bytes(codes[None, :]).reshape(-1)
             img[si] = sb
-    c = _case(img, total, chunk, off, n, k, x, xf, 1.0, 2.0 ** -4)
-    cl = _case(clean, total, chunk, off, n, k, x, xf, 1.0, 2.0 ** -4)
-    keep = np.setdiff1d(np.arange(n), rows)
-    assert np.isinf(c.wf[rows]).any(1).all() and np.isfinite(c.wf[keep]).all()
-    assert np.array_equal(c.wf[keep], cl.wf[keep])
-    fin = np.abs(c.wf[rows][np.isfinite(c.wf[rows])])
+    return rows
+
+
+def check_poisoned(wf, wf_clean, rows):
+    """The poisoned rows hold +-inf and otherwise ordinary weights, the others are those of the
+    clean image; returns the kept rows."""
+    keep = np.setdiff1d(np.arange(len(wf)), rows)
+    assert np.isinf(wf[rows]).any(1).all() and np.isfinite(wf[keep]).all()
+    assert np.array_equal(wf[keep], wf_clean[keep])
+    fin = np.abs(wf[rows][np.isfinite(wf[rows])])
     assert fin.max() <= 15  # what stays finite in those rows is ordinary
-    with np.errstate(invalid="ignore"):
-        for r in rows:
-            c.want[:, r] = (xf * c.wf[r][None, :]).sum(1)
-    assert not np.isfinite(c.want[:, rows]).any() and np.array_equal(c.want[:, keep], cl.want[:, keep])
-    c.extra.update(clean=cl, rows=rows, keep=keep)
-    return c
+    return keep
 
 
-def bad_row_expectation(xf_bad, wf, want_clean):
-    """The expectation with the bad row summed element by element (inf * 0 and inf - inf are NaN)."""
-    r = BAD_ROW[xf_bad.shape[0]]
-    want = want_clean.copy()
-    with np.errstate(invalid="ignore"):
-        want[r] = (xf_bad[r][None, :] * wf).sum(1)
-    assert not np.isfinite(want[r]).any()
-    return want
+bad_row_expectation = le.bad_row_expectation
 
 
-def nonfinite_activations(n, k, m, seed=0):
-    """A clean exact case of M = 5, 17 or 65 rows; extra["bad"] = {with_nan: (x, xf, want)} puts a
-    NaN (with_nan), a +inf and a -inf into one row of x (linear_extremes.nonfinite_x)."""
+def nonfinite_activations(n, k, m, seed=0, row=None):
+    """A clean exact case of M = 5, 17 or 65 rows (any M with `row` given); extra["bad"] =
+    {with_nan: (x, xf, want)} puts a NaN (with_nan), a +inf and a -inf into one row of x
+    (linear_extremes.nonfinite_x)."""
     c = clean_case(m, n, k, seed)
+    row = BAD_ROW[m] if row is None else row
     bad = {}
     for with_nan in (True, False):
-        xb, xbf = nonfinite_x(c.x, c.xf, with_nan)
-        bad[with_nan] = (xb, xbf, bad_row_expectation(xbf, c.wf, c.want))
-    assert np.isnan(bad[True][2][BAD_ROW[m]]).all()
-    c.extra.update(bad=bad, row=BAD_ROW[m], keep=[i for i in range(m) if i != BAD_ROW[m]])
+        xb, xbf = nonfinite_x(c.x, c.xf, with_nan, row)
+        bad[with_nan] = (xb, xbf, bad_row_expectation(xbf, c.wf, c.want, row))
+    assert np.isnan(bad[True][2][row]).all()
+    c.extra.update(bad=bad, row=row, keep=[i for i in range(m) if i != row])
     return c
 
 
@@ -202,6 +211,12 @@ class FarCase:
     need: int = 0
     first_byte: int = 0   # packed bytes of the first code byte of the parameter's first and last block
     last_byte: int = 0
+    up_s: int = -1        # swiglu: the up parameter in S (the gate is at off_s)
+    wu: np.ndarray = None
+    up_bits: np.ndarray = None
+    chunks: int = 3       # full chunks of S
+    fmt: str = "mxfp6"
+    block: int = 32
 
     def place(self, device):
         """The packed buffer on `device`: uninitialised below S."""
@@ -210,11 +225,13 @@ class FarCase:
         return buf
 
 
-def far_case(c0, off_s, m=5, seed=0, n=FAR_N):
+def far_case(c0, off_s, m=5, seed=0, n=FAR_N, up_s=-1, chunks=3):
+    """`chunks`: the full chunks of S, 3 unless a parameter of more rows (BN + 16 of the tiled
+    kernel) or a gate / up pair behind a crossing has to fit."""
     ce = FAR_CHUNK // 2
-    total_s = 3 * ce + 32 * 143  # the tail chunk holds an odd number of blocks
+    total_s = chunks * ce + 32 * 143  # the tail chunk holds an odd number of blocks
     k = FAR_K
-    assert off_s % 32 == 0 and off_s + n * k <= total_s
+    assert off_s % 32 == 0 and max(off_s, up_s) + n * k <= total_s
     x, xf = m6.int_x(m, k, 61 + seed + m)
     src_bytes = c0 * FAR_CHUNK + 2 * total_s
     elem_offset = c0 * ce + off_s
@@ -222,10 +239,15 @@ def far_case(c0, off_s, m=5, seed=0, n=FAR_N):
     need = int(_core.mxfp6_packed_size(src_bytes, FAR_CHUNK))
     assert need == c0 * FAR_PCHUNK + img.size
     fb, lb = (int(mxfp6_index(src_bytes // 2, FAR_CHUNK, e)[0]) for e in (elem_offset, elem_offset + n * k - 1))
-    bits = m6.ref_layer_bits(img, total_s, FAR_CHUNK)[off_s: off_s + n * k]
+    layer = m6.ref_layer_bits(img, total_s, FAR_CHUNK)
+    bits = layer[off_s: off_s + n * k]
     wf = m6.bits_to_f64(bits).reshape(n, k)
-    return FarCase(c0, n, img, total_s, off_s, x, xf, wf, xf @ wf.T, bits, src_bytes, elem_offset, c0 * FAR_PCHUNK, need,
-                   fb, lb)
+    c = FarCase(c0, n, img, total_s, off_s, x, xf, wf, xf @ wf.T, bits, src_bytes, elem_offset, c0 * FAR_PCHUNK, need,
+                fb, lb, chunks=chunks)
+    if up_s >= 0:
+        c.up_s, c.up_bits = up_s, layer[up_s: up_s + n * k]
+        c.wu = m6.bits_to_f64(c.up_bits).reshape(n, k)
+    return c
 
 
 def far_linear(c, buf, **kw):
@@ -233,8 +255,14 @@ def far_linear(c, buf, **kw):
                             elem_offset=c.elem_offset, **kw)
 
 
-def far_unpack(c, buf):
-    return ops.mxfp6_unpack_range(buf, c.src_bytes, FAR_CHUNK, c.elem_offset, c.n * FAR_K)
+def far_swiglu(c, buf, **kw):
+    return ops.mxfp6_swiglu(c.x.to(buf.device), buf, c.n, FAR_K, src_bytes=c.src_bytes, chunk_bytes=FAR_CHUNK,
+                            gate_offset=c.elem_offset, up_offset=c.elem_offset - c.off_s + c.up_s, **kw)
+
+
+def far_unpack(c, buf, off_s=None):
+    off = c.elem_offset - c.off_s + (c.off_s if off_s is None else off_s)
+    return ops.mxfp6_unpack_range(buf, c.src_bytes, FAR_CHUNK, off, c.n * FAR_K)
 
 
 def crossing_c0(boundary, packed):
