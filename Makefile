@@ -1,7 +1,7 @@
 # Build the native runtime in-tree for MI355X (gfx950).
 #
 #   make            -> distributed_llm_dissemination_amd/_core<ext>.so  (C++ core + HIP kernels + RCCL engine)
-#   make tools      -> bin/diskspeed (NVMe -> pinned -> HBM calibration)
+#   make tools      -> bin/diskspeed (NVMe -> pinned -> HBM calibration) and the GPU probes (bin/cvtprobe, bin/mxprobe, ...)
 #   make sanitize   -> build/tests/*_{tsan,asan} (host-only core under Thread/Address sanitizer)
 #   make sanitize-mxfp6 -> build/tests/mxfp6_selftest_asan (the MXFP6 host codec under ASan + UBSan), and runs it
 #
@@ -30,7 +30,7 @@ HIPFLAGS  := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -Icsrc -I$(ROCM)/includ
              -fvisibility=hidden
 LDFLAGS   := -shared -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64 -lrccl -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lrocprofiler-sdk-roctx -lpthread
 
-CORE_SRC  := csrc/core/vclock.cc csrc/core/json.cc csrc/core/log.cc csrc/core/wire.cc csrc/core/crc32c.cc csrc/core/fp8.cc csrc/core/mxfp4.cc csrc/core/mxfp6.cc csrc/core/trace.cc csrc/transport/inproc.cc \
+CORE_SRC  := csrc/core/vclock.cc csrc/core/json.cc csrc/core/log.cc csrc/core/wire.cc csrc/core/crc32c.cc csrc/core/fp8.cc csrc/core/mxfp4.cc csrc/core/mxfp6.cc csrc/core/mxfp8_act.cc csrc/core/trace.cc csrc/transport/inproc.cc \
              csrc/transport/tcp.cc csrc/store/store.cc csrc/sched/maxflow.cc csrc/sched/lp.cc csrc/roles/node.cc \
              csrc/roles/mode01.cc csrc/roles/mode2.cc csrc/roles/mode3.cc csrc/roles/multihost.cc \
              csrc/roles/recovery.cc csrc/roles/dispatch.cc \
@@ -58,7 +58,7 @@ $(BUILD)/%.o: csrc/%.cc $(wildcard csrc/*/*.h) Makefile
 	@mkdir -p $(dir $@)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-tools: bin/diskspeed bin/h2dbench bin/contention bin/cvtprobe bin/walkprobe
+tools: bin/diskspeed bin/h2dbench bin/contention bin/cvtprobe bin/walkprobe bin/mxprobe
 
 bin/contention: $(BUILD)/tools/contention.hip.o $(BUILD)/kernels/crc32c.hip.o $(BUILD)/kernels/fill.hip.o $(BUILD)/core/crc32c.o
 	@mkdir -p bin
@@ -68,6 +68,10 @@ bin/contention: $(BUILD)/tools/contention.hip.o $(BUILD)/kernels/crc32c.hip.o $(
 bin/cvtprobe: csrc/tools/cvtprobe.hip csrc/kernels/mxfp4_cvt.h csrc/kernels/mxfp6_cvt.h
 	@mkdir -p bin
 	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -Icsrc -Wno-unused-value -Wno-unused-result -o $@ $< -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64
+
+bin/mxprobe: csrc/tools/mxprobe.hip
+	@mkdir -p bin
+	$(HIPCC) -O2 -std=c++17 --offload-arch=$(ARCH) -Wno-unused-value -Wno-unused-result -o $@ $< -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64
 
 bin/walkprobe: csrc/tools/walkprobe.hip
 	@mkdir -p bin

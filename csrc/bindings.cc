@@ -10,6 +10,7 @@
 #include "core/fp8.h"
 #include "core/mxfp4.h"
 #include "core/mxfp6.h"
+#include "core/mxfp8_act.h"
 #include "core/log.h"
 #include "core/ratelimit.h"
 #include "core/trace.h"
@@ -558,6 +559,12 @@ PYBIND11_MODULE(_core, m) {
                            reinterpret_cast<uint16_t*>(out));
   }, py::arg("packed"), py::arg("packed_bytes"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("block"),
      py::arg("elem_off"), py::arg("n"), py::arg("out"));
+  // MXFP8 activations (core/mxfp8_act.h), host reference: `n` bf16 in host memory at `x` -> n codes, n / 32 scale bytes
+  m.def("mxfp8_quantize_rows_host", [](uint64_t x, int64_t n, uint64_t codes, uint64_t scales) {
+    py::gil_scoped_release nogil;
+    mxfp8::quantize_host(reinterpret_cast<const uint16_t*>(x), n, reinterpret_cast<uint8_t*>(codes),
+                         reinterpret_cast<uint8_t*>(scales));
+  }, py::arg("x"), py::arg("n"), py::arg("codes"), py::arg("scales"));
   // MXFP4 wire/storage format (core/mxfp4.h), host reference
   m.def("mxfp4_packed_size", &mxfp4::packed_size, py::arg("src_bytes"), py::arg("src_chunk"));
   m.def("mxfp4_source_size", &mxfp4::source_size, py::arg("packed"), py::arg("src_chunk"));

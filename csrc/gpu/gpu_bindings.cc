@@ -587,6 +587,36 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("stream") = 0);
   // (BM, BN): rows of x and rows of W of a workgroup's output tile in the tiled kernels
   m.def("mxfp4_tiled_tile", []() { return std::make_pair(kern::kMxfp4TiledBM, kern::kMxfp4TiledBN); });
+  // bf16 x [m, k] -> MXFP8 activations: codes [m, k] and scale bytes [m, k / 32] (kernels/mxfp8_act.hip)
+  m.def("mxfp8_quantize_rows", [](uint64_t x, int64_t m_rows, int64_t k, uint64_t codes, uint64_t scales,
+                                  uint64_t stream) {
+    check(kern::mxfp8_quantize_rows(reinterpret_cast<const uint16_t*>(x), m_rows, k, reinterpret_cast<uint8_t*>(codes),
+                                    reinterpret_cast<uint8_t*>(scales), as_stream(stream)),
+          "mxfp8_quantize_rows");
+  }, py::arg("x"), py::arg("m"), py::arg("k"), py::arg("codes"), py::arg("scales"), py::arg("stream") = 0);
+  // W4A8 on the block-scaled MFMA: the tiled pair's contract with x as (codes, scales) (kernels/mxfp4_mx.hip)
+  m.def("mxfp4_linear_mx", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off,
+                              uint64_t x_codes, uint64_t x_scales, int64_t m_rows, int64_t n, int64_t k, uint64_t y,
+                              int64_t ldy, bool y_bf16, uint64_t stream) {
+    check(kern::mxfp4_linear_mx(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, elem_off,
+                                reinterpret_cast<const uint8_t*>(x_codes), reinterpret_cast<const uint8_t*>(x_scales),
+                                m_rows, n, k, reinterpret_cast<void*>(y), ldy, y_bf16, as_stream(stream)),
+          "mxfp4_linear_mx");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("elem_off"), py::arg("x_codes"),
+     py::arg("x_scales"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
+     py::arg("stream") = 0);
+  m.def("mxfp4_swiglu_mx", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off,
+                              int64_t up_off, uint64_t x_codes, uint64_t x_scales, int64_t m_rows, int64_t n,
+                              int64_t k, uint64_t y, int64_t ldy, bool y_bf16, uint64_t stream) {
+    check(kern::mxfp4_swiglu_mx(reinterpret_cast<const void*>(packed), src_bytes, src_chunk, gate_off, up_off,
+                                reinterpret_cast<const uint8_t*>(x_codes), reinterpret_cast<const uint8_t*>(x_scales),
+                                m_rows, n, k, reinterpret_cast<void*>(y), ldy, y_bf16, as_stream(stream)),
+          "mxfp4_swiglu_mx");
+  }, py::arg("packed"), py::arg("src_bytes"), py::arg("src_chunk"), py::arg("gate_off"), py::arg("up_off"),
+     py::arg("x_codes"), py::arg("x_scales"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"),
+     py::arg("y_bf16"), py::arg("stream") = 0);
+  // (BM, BN) of the W4A8 kernels
+  m.def("mxfp4_mx_tile", []() { return std::make_pair(kern::kMxfp4MxBM, kern::kMxfp4MxBN); });
   // W8A16 linear from the fp8-packed layer in place (kernels/fp8_linear.hip); stream-ordered
   m.def("fp8_linear", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
                          uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,

@@ -172,6 +172,33 @@ hipError_t mxfp4_swiglu_tiled(const void* packed, int64_t src_bytes, int64_t src
                               int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
                               bool y_bf16, hipStream_t s);
 
+// ---- mxfp8_act.hip: bf16 x [M, K] (contiguous, 16-B aligned, K a multiple of 32)
+// -> MXFP8 activations (core/mxfp8_act.h): e4m3fn codes [M, K] (8-B aligned) and one
+// E8M0 scale byte per 32 values along K, [M, K / 32]; byte for byte
+// mxfp8::quantize_host on every input. One launch for any M, stream-ordered, no
+// allocation.
+hipError_t mxfp8_quantize_rows(const uint16_t* x, int64_t M, int64_t K, uint8_t* codes, uint8_t* scales,
+                               hipStream_t s);
+
+// ---- mxfp4_mx.hip: W4A8 on the block-scaled MFMA. The contract is
+// mxfp4_linear_tiled's / mxfp4_swiglu_tiled's in every respect except that x
+// arrives quantized, as the codes [M, K] (contiguous, 16-B aligned) and scale
+// bytes [M, K / 32] (contiguous) of mxfp8_quantize_rows: y[m][n] = sum_k x^[m][k]
+// * W[n][k] with x^ = code * 2^(byte - 127), one f32 accumulator per element on
+// v_mfma_scale_f32_16x16x128_f8f6f4 walking K in steps of 128 in ascending order
+// (batch invariance; g and u of the gated kernel are the linear's f32 results bit
+// for bit). A NaN code in x^ gives a NaN row and a weight scale byte 0xFF a NaN
+// column. Nothing is read outside the two x arrays and the parameters' blocks and
+// scale bytes, nothing written outside y[:M, :N]. One launch for any M,
+// stream-ordered, no allocation, no workspace, no atomics.
+constexpr int kMxfp4MxBM = 128, kMxfp4MxBN = 128;
+hipError_t mxfp4_linear_mx(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off,
+                           const uint8_t* x_codes, const uint8_t* x_scales, int64_t M, int64_t N, int64_t K, void* y,
+                           int64_t ldy, bool y_bf16, hipStream_t s);
+hipError_t mxfp4_swiglu_mx(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
+                           const uint8_t* x_codes, const uint8_t* x_scales, int64_t M, int64_t N, int64_t K, void* y,
+                           int64_t ldy, bool y_bf16, hipStream_t s);
+
 // ---- fp8_linear.hip: the same product with W read in place from an fp8-packed
 // layer (core/fp8.h: e4m3 codes and one power-of-two f32 scale per `block`
 // elements, per source chunk; fp8::unpack_range_host defines where an element

@@ -50,7 +50,7 @@ on received weights against the originals.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Tuple, Union
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 import torch.nn.functional as F
@@ -225,15 +225,25 @@ def unflatten_packed(packed: torch.Tensor, spec: DecoderSpec, chunk_bytes: int, 
     return out
 
 
-def _linear(x: torch.Tensor, w: Param, tiled: bool = False) -> torch.Tensor:
+def _check_act_fmt(w: "PackedParam", act: Optional[str]) -> None:
+    if act is not None and w.fmt != "mxfp4":
+        raise ValueError(f"act={act!r} runs MXFP4-packed projections only, this one is packed as {w.fmt}")
+
+
+def _linear(x: torch.Tensor, w: Param, tiled: bool = False, act: Optional[str] = None) -> torch.Tensor:
     """x @ w.T: from the packed bytes for a PackedParam (ops.mxfp4_linear, ops.mxfp6_linear
     or ops.fp8_linear by its format), F.linear for a tensor. `tiled`: the many-row kernel
-    of a PackedParam's format (tiled=True of the same op); a tensor has none."""
+    of a PackedParam's format (tiled=True of the same op); a tensor has none. `act`: the
+    op's act= for an MXFP4 PackedParam, a ValueError for another format, nothing for a
+    tensor."""
     if isinstance(w, PackedParam):
         from ..ops import fp8_linear, mxfp4_linear, mxfp6_linear
 
-        # `tiled` is passed only when set: without it the call is what it always was
+        _check_act_fmt(w, act)
+        # `tiled` and `act` are passed only when set: without them the call is what it always was
         kw = {"tiled": True} if tiled else {}
+        if act is not None:
+            kw["act"] = act
         if w.fmt == "mxfp6":
             return mxfp6_linear(x, w.packed, w.shape[0], w.shape[1], src_bytes=w.src_bytes,
                                 chunk_bytes=w.chunk_bytes, elem_offset=w.elem_offset, out_dtype=x.dtype, **kw)
@@ -275,7 +285,7 @@ def _same_layer(*ws: Param) -> bool:
                and w.fmt == ws[0].fmt and w.block == ws[0].block for w in ws[1:])
 
 
-def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool, tiled: bool = False):
+def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool, tiled: bool = False, act: Optional[str] = None):
     """q, k and v of h. On the GPU, three PackedParams of one layer that lie one behind
     the other with equal in_features are one [h + 2 kv, h] weight and take one launch;
     the result is split by views. On the CPU (and for anything else) one call each."""
@@ -285,35 +295,39 @@ def _qkv(h: torch.Tensor, p: Dict[str, Param], fuse: bool, tiled: bool = False):
             and wv.elem_offset == wk.elem_offset + _numel(wk.shape)):
         nq, nk, nv = wq.shape[0], wk.shape[0], wv.shape[0]
         y = _linear(h, PackedParam(wq.packed, wq.src_bytes, wq.chunk_bytes, wq.elem_offset, (nq + nk + nv, wq.shape[1]),
-                                   wq.fmt, wq.block), tiled)
+                                   wq.fmt, wq.block), tiled, act)
         return y[..., :nq], y[..., nq:nq + nk], y[..., nq + nk:]
-    return _linear(h, wq, tiled), _linear(h, wk, tiled), _linear(h, wv, tiled)
+    return _linear(h, wq, tiled, act), _linear(h, wk, tiled, act), _linear(h, wv, tiled, act)
 
 
 def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool = False,
-           tiled: bool = False) -> torch.Tensor:
+           tiled: bool = False, act: Optional[str] = None) -> torch.Tensor:
     """silu(h @ wg.T) * (h @ wu.T): one ops.mxfp4_swiglu for two MXFP4 PackedParams of
     one layer with equal shapes (on the CPU the very ops of the other route). Two fp8 or
     two MXFP6 PackedParams take one ops.fp8_swiglu / ops.mxfp6_swiglu only with
     `fuse_gated` as well (opt-in) and otherwise one linear each, as does anything else.
     `tiled` goes to whichever call is made: the fused op's tiled=True, or `_linear`'s - two
-    tiled linears and the torch epilogue for fp8 and MXFP6 without `fuse_gated`."""
+    tiled linears and the torch epilogue for fp8 and MXFP6 without `fuse_gated`. `act`
+    goes the same way (MXFP4 only; another packed format raises ValueError)."""
     if fuse and _same_layer(wg, wu) and wg.shape == wu.shape:
         from ..ops import fp8_swiglu, mxfp4_swiglu, mxfp6_swiglu
 
+        _check_act_fmt(wg, act)
         kw = dict(src_bytes=wg.src_bytes, chunk_bytes=wg.chunk_bytes, gate_offset=wg.elem_offset,
                   up_offset=wu.elem_offset, out_dtype=h.dtype, **({"tiled": True} if tiled else {}))
+        if act is not None:
+            kw["act"] = act
         if wg.fmt == "mxfp4":
             return mxfp4_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
         if fuse_gated and wg.fmt == "mxfp6":
             return mxfp6_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], **kw)
         if fuse_gated and wg.fmt == "fp8":
             return fp8_swiglu(h, wg.packed, wg.shape[0], wg.shape[1], block=wg.block, **kw)
-    return F.silu(_linear(h, wg, tiled)) * _linear(h, wu, tiled)
+    return F.silu(_linear(h, wg, tiled, act)) * _linear(h, wu, tiled, act)
 
 
 def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True,
-                    fuse_gated: bool = False, tiled: bool = False) -> torch.Tensor:
+                    fuse_gated: bool = False, tiled: bool = False, act: Optional[str] = None) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
     packed bytes (ops.mxfp4_linear, ops.mxfp6_linear or ops.fp8_linear), a packed norm
@@ -329,11 +343,20 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     `fuse_gated`, 4 weight launches for any batch * seq instead of 4 per 64 rows (fp8
     and MXFP6 without `fuse_gated`: 5, gate and up as two tiled linears), each row of a
     projection a function of that row of its input alone. It is ignored for plain
-    tensors, and on the CPU it changes nothing."""
+    tensors, and on the CPU it changes nothing.
+    `act="mxfp8"` (opt-in) runs every MXFP4-packed projection as W4A8 (act= of
+    ops.mxfp4_linear / ops.mxfp4_swiglu): the projection's input is quantized to MXFP8
+    and multiplied on the block-scaled MFMA - four quantize and four matmul launches
+    for any batch * seq with `fuse`. The result is that of the quantized activations,
+    not of the W4A16 routes. A packed projection of another format raises ValueError
+    instead of silently running W.A16; plain tensors are untouched; any other `act`
+    raises ValueError."""
+    if act not in (None, "mxfp8"):
+        raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
-    q, k, v = _qkv(h, p, fuse, tiled)
+    q, k, v = _qkv(h, p, fuse, tiled, act)
     q = q.view(b, s, nh, hd).transpose(1, 2)
     k = k.view(b, s, nkv, hd).transpose(1, 2)
     v = v.view(b, s, nkv, hd).transpose(1, 2)
@@ -341,6 +364,7 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     k = k.repeat_interleave(nh // nkv, dim=1)
     v = v.repeat_interleave(nh // nkv, dim=1)
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-    x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"], tiled)
+    x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"], tiled, act)
     h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled), p["down_proj"], tiled)
+    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled, act), p["down_proj"], tiled,
+                       act)

@@ -569,6 +569,55 @@ def mxfp6_unpack_range(packed: torch.Tensor, src_bytes: int, chunk_bytes: int, e
     return out
 
 
+# ---- MXFP8 activations (core/mxfp8_act.h): e4m3fn codes and one E8M0 scale byte per 32
+# values along the last dimension, the x side of the W4A8 route (act="mxfp8")
+
+def mxfp8_quantize_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """bf16 `x` [..., K] (K a multiple of 32) -> (codes uint8 [..., K], scales uint8
+    [..., K / 32]): OCP e4m3fn codes and one E8M0 byte per 32 values along K. Scale,
+    codes, saturation (+-inf become the largest code) and NaN (0x7F | sign) are those
+    of `fp8_pack(x, block=32)`, byte for byte, and the scale byte is the exponent of
+    its f32 scale; the value is ``code * 2**(byte - 127)``. GPU: one launch on the
+    current stream for any number of rows; CPU: the host codec, the same bytes."""
+    if x.dtype != torch.bfloat16:
+        raise ValueError(f"x must be {torch.bfloat16}, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] <= 0 or x.shape[-1] % _MX_BLOCK or x.numel() == 0:
+        raise ValueError(f"x must be [..., K] with K a positive multiple of {_MX_BLOCK} and at least one row, "
+                         f"got {tuple(x.shape)}")
+    k = x.shape[-1]
+    x2 = x.reshape(-1, k)
+    if not x2.is_contiguous():
+        x2 = x2.contiguous()
+    if x2.data_ptr() % 16:
+        x2 = x2.clone()
+    m = x2.shape[0]
+    codes = torch.empty(m, k, dtype=torch.uint8, device=x.device)
+    scales = torch.empty(m, k // _MX_BLOCK, dtype=torch.uint8, device=x.device)
+    if x.is_cuda:
+        _core.mxfp8_quantize_rows(x2.data_ptr(), m, k, codes.data_ptr(), scales.data_ptr(), _stream())
+    else:
+        _core.mxfp8_quantize_rows_host(x2.data_ptr(), m * k, codes.data_ptr(), scales.data_ptr())
+    return codes.view(*x.shape[:-1], k), scales.view(*x.shape[:-1], k // _MX_BLOCK)
+
+
+def _mxfp8_values(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """code * 2^(byte - 127) as f32 [rows, K]: exact (at most 2^-135, at least 448 * 2^120)."""
+    k = codes.shape[-1]
+    v = codes.reshape(-1, k // _MX_BLOCK, _MX_BLOCK).view(torch.float8_e4m3fn).float()
+    return torch.ldexp(v, scales.reshape(-1, k // _MX_BLOCK, 1).to(torch.int32) - 127).view(-1, k)
+
+
+def _check_act(act: Optional[str], split_k: int, row_tiles: int) -> None:
+    if act is None:
+        return
+    if act != "mxfp8":
+        raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
+    if split_k:
+        raise ValueError("split_k must be 0 with act='mxfp8': the native kernel never splits K")
+    if row_tiles:
+        raise ValueError("row_tiles must be 0 with act='mxfp8': the native kernel has one tile shape")
+
+
 def _check_tiled(tiled: bool, split_k: int, row_tiles: int) -> None:
     if tiled and split_k:
         raise ValueError("split_k must be 0 with tiled=True: the tiled kernel never splits K")
@@ -579,7 +628,7 @@ def _check_tiled(tiled: bool, split_k: int, row_tiles: int) -> None:
 def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                  chunk_bytes: int, elem_offset: int = 0, out_dtype: torch.dtype = torch.bfloat16,
                  split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
-                 tiled: bool = False) -> torch.Tensor:
+                 tiled: bool = False, act: Optional[str] = None) -> torch.Tensor:
     """``x @ W.T`` for a bf16 `x` [..., in_features] and the [out_features, in_features]
     weight stored as elements [elem_offset, ...) of the MXFP4-packed layer `packed`
     (`src_bytes` of bf16 in chunks of `chunk_bytes`, the layout of `mxfp4_pack_layer`).
@@ -598,8 +647,24 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     (mxfp4_tiled.hip) - one launch for any number of rows, x shared through LDS, W
     read once per `_core.mxfp4_tiled_tile()[0]` rows instead of once per 64. K is
     never split there, so a row of the result depends on that row of x alone (the
-    same bits in any batch); `split_k` and `row_tiles` must stay 0."""
+    same bits in any batch); `split_k` and `row_tiles` must stay 0.
+    `act="mxfp8"` (opt-in, W4A8): x is quantized to MXFP8 (`mxfp8_quantize_rows`) on
+    the current stream and the product runs on the block-scaled MFMA
+    (mxfp4_mx.hip), codes and scale bytes of both sides as they lie in memory: two
+    launches for any number of rows. The result is ``sum_k x^[m][k] * w^[n][k]`` with
+    x^ the quantized activation, one f32 accumulator per element walking K in
+    ascending order (batch invariant like the tiled kernel). It is the only kernel
+    for `act`, so `tiled` may be either and `split_k` and `row_tiles` must stay 0.
+    +-inf in x saturates to the largest code of its block (core/fp8.h) where the
+    W4A16 kernels carry it through; a NaN in x gives a NaN row; a weight block with
+    scale byte 0xFF gives a NaN column. The instruction drops a product 2^14 or
+    more below the largest of its group of 8 consecutive k, so the kernel issues
+    three MFMAs per step, one per exponent class of x^ (mxfp4_mx.hip's header):
+    the result is an f32-accurate sum also on inputs with outliers, at a third of
+    the instruction's rate. CPU: the host codec,
+    x^ and w^ in f32, ``F.linear`` in f32; a bf16 result is that rounded once."""
     _check_tiled(tiled, split_k, row_tiles)
+    _check_act(act, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -625,7 +690,9 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
         if out is not None:
             raise ValueError("out is for GPU tensors")
         w = mxfp4_unpack_range(packed, src_bytes, chunk_bytes, elem_offset, n * k).view(n, k)
-        if out_dtype == torch.float32:
+        if act is not None:
+            y = torch.nn.functional.linear(_mxfp8_values(*mxfp8_quantize_rows(x2)), w.float()).to(out_dtype)
+        elif out_dtype == torch.float32:
             y = torch.nn.functional.linear(x2.float(), w.float())
         else:
             y = torch.nn.functional.linear(x2, w)
@@ -641,6 +708,11 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if act is not None:
+        xq, xs = mxfp8_quantize_rows(x2)
+        _core.mxfp4_linear_mx(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, xq.data_ptr(), xs.data_ptr(), m,
+                              n, k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+        return y if out is not None else y.view(*lead, n)
     if tiled:
         _core.mxfp4_linear_tiled(packed.data_ptr(), src_bytes, chunk_bytes, elem_offset, x2.data_ptr(), m, n, k,
                                  y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
@@ -850,7 +922,7 @@ def mxfp6_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
 def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_features: int, *, src_bytes: int,
                  chunk_bytes: int, gate_offset: int, up_offset: int, out_dtype: torch.dtype = torch.bfloat16,
                  split_k: int = 0, row_tiles: int = 0, out: Optional[torch.Tensor] = None,
-                 tiled: bool = False) -> torch.Tensor:
+                 tiled: bool = False, act: Optional[str] = None) -> torch.Tensor:
     """``silu(x @ Wg.T) * (x @ Wu.T)``, the front half of a gated MLP, for a bf16 `x`
     [..., in_features] and two [out_features, in_features] weights stored as elements
     [gate_offset, ...) and [up_offset, ...) of the MXFP4-packed layer `packed` (as in
@@ -866,8 +938,14 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     ``F.silu(F.linear(x, wg)) * F.linear(x, wu)`` - in f32 for an f32 result, in bf16
     (what plain bf16 weights get, op for op) for a bf16 one.
     `out` (GPU only) as in `mxfp4_linear`. `tiled` as in `mxfp4_linear`: the gated
-    kernel for many rows, whose g and u are bit for bit the tiled linear's f32 results."""
+    kernel for many rows, whose g and u are bit for bit the tiled linear's f32 results.
+    `act="mxfp8"` as in `mxfp4_linear` (quantize, then the gated kernel of
+    mxfp4_mx.hip: two launches): g and u are bit for bit the f32 results of
+    `mxfp4_linear(..., act="mxfp8")`, with its handling of +-inf, NaN and 0xFF scale
+    bytes; the epilogue is the same. CPU: x^, wg^ and wu^ in f32, the expression above
+    in f32; a bf16 result is that rounded once."""
     _check_tiled(tiled, split_k, row_tiles)
+    _check_act(act, split_k, row_tiles)
     if out is not None:
         out_dtype = out.dtype
     if out_dtype not in (torch.bfloat16, torch.float32):
@@ -895,10 +973,12 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
             raise ValueError("out is for GPU tensors")
         wg = mxfp4_unpack_range(packed, src_bytes, chunk_bytes, gate_offset, n * k).view(n, k)
         wu = mxfp4_unpack_range(packed, src_bytes, chunk_bytes, up_offset, n * k).view(n, k)
-        if out_dtype == torch.float32:
+        if act is not None:
+            x2, wg, wu = _mxfp8_values(*mxfp8_quantize_rows(x2)), wg.float(), wu.float()
+        elif out_dtype == torch.float32:
             x2, wg, wu = x2.float(), wg.float(), wu.float()
         y = torch.nn.functional.silu(torch.nn.functional.linear(x2, wg)) * torch.nn.functional.linear(x2, wu)
-        return y.view(*lead, n)
+        return y.to(out_dtype).view(*lead, n)
     if not x2.is_contiguous():
         x2 = x2.contiguous()
     if x2.data_ptr() % 16:
@@ -910,6 +990,11 @@ def mxfp4_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
         y = out
         if y.device != x.device or tuple(y.shape) != (m, n) or y.stride(1) != 1 or y.stride(0) < n:
             raise ValueError(f"out must be [{m}, {n}] on x's device with unit stride along rows")
+    if act is not None:
+        xq, xs = mxfp8_quantize_rows(x2)
+        _core.mxfp4_swiglu_mx(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, xq.data_ptr(),
+                              xs.data_ptr(), m, n, k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
+        return y if out is not None else y.view(*lead, n)
     if tiled:
         _core.mxfp4_swiglu_tiled(packed.data_ptr(), src_bytes, chunk_bytes, gate_offset, up_offset, x2.data_ptr(), m, n,
                                  k, y.data_ptr(), y.stride(0), out_dtype == torch.bfloat16, _stream())
