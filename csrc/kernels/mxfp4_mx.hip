@@ -44,9 +44,13 @@
 // Within a class all bits of all products code * e2m1 lie within 2^12 of each
 // other under one pair of scales, so each MFMA adds its groups exactly and what
 // is left is the f32 accumulation across groups, blocks and steps.
-// (core/mxfp4.h's dequantized weight is a bf16 and can differ from
-// code * 2^(byte - 127) at the ends of the scale range, where no test asserts
-// anything.)
+// (core/mxfp4.h's dequantized weight is a bf16. It equals code * 2^(byte - 127),
+// the value the instruction multiplies, for every code under every scale byte
+// 0..254 - down to 2^-128, a bf16 subnormal - except the 12 pairs whose value
+// reaches 2^128: the magnitudes 4 and 6 (nibbles 6, 7) under byte 253 and 2, 3,
+// 4 and 6 (nibbles 4..7) under byte 254, either sign, which are +-inf on the
+// host route and finite factors here.
+// tests/test_mx_operands_host.py lists them.)
 //
 // K walk: steps of 128, three MFMAs (the classes, in ascending order) per (row
 // tile, weight tile) per step. In step s

@@ -662,7 +662,12 @@ def mxfp4_linear(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_fe
     three MFMAs per step, one per exponent class of x^ (mxfp4_mx.hip's header):
     the result is an f32-accurate sum also on inputs with outliers, at a third of
     the instruction's rate. CPU: the host codec,
-    x^ and w^ in f32, ``F.linear`` in f32; a bf16 result is that rounded once."""
+    x^ and w^ in f32, ``F.linear`` in f32; a bf16 result is that rounded once.
+    The CPU route's w^ is the bf16 of `mxfp4_unpack_range`, the GPU multiplies
+    ``code * 2**(byte - 127)``: the two are equal for every code under every scale
+    byte 0..254 except the 12 pairs that reach 2**128 (the magnitudes 4 and 6, i.e.
+    nibbles 6 and 7, under byte 253; 2, 3, 4 and 6, nibbles 4..7, under byte 254;
+    either sign), which are +-inf on the CPU route."""
     _check_tiled(tiled, split_k, row_tiles)
     _check_act(act, split_k, row_tiles)
     if out is not None:

@@ -7,8 +7,9 @@ The references are those of test_mxfp4_mx_host.py: the quantizer is held to the 
 for byte, the products to float64 of (x^, w^) with x^ dequantized in numpy from the HOST codec's
 bytes and w^ the numpy reference of test_mxfp4_linear_host.py. The cases are those of
 test_gpu_mxfp4_tiled.py at this kernel's own tile (BM, BN from the binding), the contract -
-batch invariance - is the same. Nothing here asserts what the instruction does with subnormal
-products or with scale bytes at the ends of the range (csrc/tools/mxprobe.hip records it)."""
+batch invariance - is the same. Every x here is what the quantizer makes of it; hand-made codes
+and scale bytes (subnormal products, both ends of both scale ranges, every e4m3 code, NaN scales
+and codes) and the addressing extremes are in test_gpu_mxfp4_mx_extremes.py."""
 import os
 
 import numpy as np
