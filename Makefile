@@ -4,6 +4,7 @@
 #   make tools      -> bin/diskspeed (NVMe -> pinned -> HBM calibration) and the GPU probes (bin/cvtprobe, bin/mxprobe, ...)
 #   make sanitize   -> build/tests/*_{tsan,asan} (host-only core under Thread/Address sanitizer)
 #   make sanitize-mxfp6 -> build/tests/mxfp6_selftest_asan (the MXFP6 host codec under ASan + UBSan), and runs it
+#   make sanitize-attn  -> build/tests/attn_decode_selftest_asan (the attention's launch sizing under ASan + UBSan), and runs it
 #
 # The extension links the HIP runtime and RCCL that PyTorch-ROCm ships, so one
 # process never holds two HIP runtimes (torch is imported before _core).
@@ -109,7 +110,18 @@ $(BUILD)/tests/mxfp6_selftest_asan: csrc/tests/mxfp6_selftest.cc csrc/core/mxfp6
 sanitize-mxfp6: $(BUILD)/tests/mxfp6_selftest_asan
 	$(BUILD)/tests/mxfp6_selftest_asan
 
+# The host-side sizing of the single-token attention (kernels/attn_decode_plan.h)
+# with its own main: an exact-size workspace walked with the kernels' own index
+# arithmetic, and the contract's extremes, under ASan + UBSan.
+$(BUILD)/tests/attn_decode_selftest_asan: csrc/tests/attn_decode_selftest.cc csrc/kernels/attn_decode_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	  -static-libasan -static-libubsan -o $@ csrc/tests/attn_decode_selftest.cc
+
+sanitize-attn: $(BUILD)/tests/attn_decode_selftest_asan
+	$(BUILD)/tests/attn_decode_selftest_asan
+
 clean:
 	rm -rf $(BUILD) $(PKG)/_core*.so bin/diskspeed bin/h2dbench bin/contention
 
-.PHONY: all tools sanitize sanitize-mxfp6 clean
+.PHONY: all tools sanitize sanitize-mxfp6 sanitize-attn clean

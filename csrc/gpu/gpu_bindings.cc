@@ -22,6 +22,7 @@
 #include "core/mxfp6.h"
 #include "gpu/gpu_api.h"
 #include "gpu/hip_backend.h"
+#include "kernels/attn_decode_plan.h"
 #include "kernels/kernels.h"
 
 namespace py = pybind11;
@@ -709,6 +710,36 @@ void register_gpu_bindings(PyObject* module) {
   // (BM, BN) of those kernels, per format
   m.def("mxfp6_tiled_tile", []() { return std::make_pair(kern::kMxfp6TiledBM, kern::kMxfp6TiledBN); });
   m.def("fp8_tiled_tile", []() { return std::make_pair(kern::kFp8TiledBM, kern::kFp8TiledBN); });
+  // one decode step's attention against a KV cache (kernels/attn_decode.hip); stream-ordered
+  m.def("attn_rope_append", [](uint64_t q, int64_t ldq, uint64_t k, int64_t ldk, uint64_t v, int64_t ldv, uint64_t pos,
+                               uint64_t cos, uint64_t sin, int64_t b, int64_t heads, int64_t kv_heads, int64_t d,
+                               int64_t capacity, uint64_t q_out, uint64_t k_cache, uint64_t v_cache, uint64_t stream) {
+    check(kern::attn_rope_append(reinterpret_cast<const uint16_t*>(q), ldq, reinterpret_cast<const uint16_t*>(k), ldk,
+                                 reinterpret_cast<const uint16_t*>(v), ldv, reinterpret_cast<const int32_t*>(pos),
+                                 reinterpret_cast<const float*>(cos), reinterpret_cast<const float*>(sin), b, heads,
+                                 kv_heads, d, capacity, reinterpret_cast<uint16_t*>(q_out),
+                                 reinterpret_cast<uint16_t*>(k_cache), reinterpret_cast<uint16_t*>(v_cache),
+                                 as_stream(stream)),
+          "attn_rope_append");
+  }, py::arg("q"), py::arg("ldq"), py::arg("k"), py::arg("ldk"), py::arg("v"), py::arg("ldv"), py::arg("pos"),
+     py::arg("cos"), py::arg("sin"), py::arg("b"), py::arg("heads"), py::arg("kv_heads"), py::arg("d"),
+     py::arg("capacity"), py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("stream") = 0);
+  m.def("attn_decode", [](uint64_t q, uint64_t k_cache, uint64_t v_cache, uint64_t lens, int64_t b, int64_t heads,
+                          int64_t kv_heads, int64_t d, int64_t capacity, int64_t max_len, uint64_t ws, int64_t ws_bytes,
+                          uint64_t y, bool y_bf16, uint64_t stream) {
+    check(kern::attn_decode(reinterpret_cast<const uint16_t*>(q), reinterpret_cast<const uint16_t*>(k_cache),
+                            reinterpret_cast<const uint16_t*>(v_cache), reinterpret_cast<const int32_t*>(lens), b, heads,
+                            kv_heads, d, capacity, max_len, reinterpret_cast<void*>(ws), ws_bytes,
+                            reinterpret_cast<void*>(y), y_bf16, as_stream(stream)),
+          "attn_decode");
+  }, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("lens"), py::arg("b"), py::arg("heads"),
+     py::arg("kv_heads"), py::arg("d"), py::arg("capacity"), py::arg("max_len"), py::arg("ws"), py::arg("ws_bytes"),
+     py::arg("y"), py::arg("y_bf16"), py::arg("stream") = 0);
+  // bytes of attn_decode's workspace (-1: a shape the kernel does not serve)
+  m.def("attn_decode_workspace_bytes", &kern::attn_decode_workspace_bytes, py::arg("b"), py::arg("heads"),
+        py::arg("kv_heads"), py::arg("d"), py::arg("capacity"), py::arg("max_len"));
+  // positions of one workgroup's chunk: chunk boundaries are multiples of it for every batch
+  m.def("attn_decode_chunk", []() { return kern::kAttnDecodeChunk; });
 
   // ---- RCCL path on one GPU: a one-rank communicator driven through the same
   // Backend::group / crc calls the planned engine issues. `rounds` groups of

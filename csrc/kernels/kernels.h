@@ -277,5 +277,45 @@ hipError_t fp8_swiglu_tiled(const void* packed, int64_t src_bytes, int64_t src_c
                             int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
                             bool y_bf16, hipStream_t s);
 
+// ---- attn_decode.hip: one decode step's attention against a KV cache in HBM.
+// The caches are bf16 [B, kv_heads, capacity, d], contiguous and 16-B aligned,
+// d 32, 64 or 128, capacity at most 2^20 positions; every cache index is 64-bit.
+//
+// attn_rope_append, ONE launch: for every sequence b with 0 <= pos[b] < capacity
+// (pos int32 on the device), q_out[b, h] = rope(q[b, h]) at position pos[b]
+// (q_out bf16 [B, heads, d], contiguous), k_cache[b, h, pos[b]] = rope(k[b, h])
+// and v_cache[b, h, pos[b]] = v[b, h]. q, k and v are bf16 rows with unit stride
+// and row strides ldq, ldk, ldv elements (three slices of one merged projection
+// or three buffers). rope(x) = x * cos + rot(x) * sin in f32 from the tables cos,
+// sin f32 [capacity, d]: two products and one sum, each rounded (no FMA), then
+// one rounding to bf16. A pos[b] outside [0, capacity) writes nothing to the
+// caches and a zero q_out row.
+//
+// attn_decode: y[b, h * d ...] = softmax(q[b, h] . K[b, h / group, :lens[b]] /
+// sqrt(d)) V[b, h / group, :lens[b]] for q bf16 [B, heads, d] (contiguous, 16-B
+// aligned), lens int32 [B] on the device with 0 <= lens[b] <= max_len <=
+// capacity (a larger lens[b] is clamped to the capacity and never reads out of
+// bounds, but its row is then unspecified), group = heads / kv_heads in 1..16; y
+// is [B, heads * d] f32 or bf16 (the f32 result rounded to nearest even).
+// lens[b] = 0 gives a zero row. A workgroup serves one (b, KV head, chunk of
+// kAttnDecodeChunk positions) and the KV head's whole group, so K and V rows are
+// read once per KV head; scores and the online softmax are f32, P is rounded to
+// bf16 for P V on v_mfma_f32_16x16x32_bf16; chunk partials (m, l, o) are f32 in
+// `ws` (attn_decode_workspace_bytes, 16-B aligned; -1 for an unsupported shape)
+// and a second launch merges them in ascending chunk order. Chunk c is positions
+// [c * kAttnDecodeChunk, ...) whatever B, the other lens, max_len and capacity
+// are, so row b is a function of q[b] and the valid K and V rows of b alone: the
+// same bits in any batch. No position at or behind lens[b] is ever loaded.
+// Stream-ordered, no allocation, no atomics. Anything else: hipErrorInvalidValue.
+hipError_t attn_rope_append(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
+                            int64_t ldv, const int32_t* pos, const float* cos, const float* sin, int64_t B,
+                            int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, uint16_t* q_out,
+                            uint16_t* k_cache, uint16_t* v_cache, hipStream_t s);
+int64_t attn_decode_workspace_bytes(int64_t B, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity,
+                                    int64_t max_len);
+hipError_t attn_decode(const uint16_t* q, const uint16_t* k_cache, const uint16_t* v_cache, const int32_t* lens,
+                       int64_t B, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, int64_t max_len,
+                       void* ws, int64_t ws_bytes, void* y, bool y_bf16, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

@@ -45,6 +45,19 @@ row of a projection a function of that row of its input alone.
 ``decoder_forward`` is a plain PyTorch reference of the layer (RMSNorm,
 grouped-query attention with rotary embeddings, SwiGLU MLP) that the tests run
 on received weights against the originals.
+
+Generating a token does not re-run the prefix: ``decoder_step`` (opt-in) is one decode
+step of the same layer against a ``KVCache`` in HBM.
+
+    cache = KVCache.allocate(spec, batch, capacity, device="cuda")
+    y = decoder_forward(x, params, spec, cache=cache)     # the prefill: also fills positions [0, seq)
+    y1 = decoder_step(x1, params, spec, cache)            # x1 [batch, 1, hidden]: one more token each
+
+The step runs the projections on the routes above (their 1 .. 16 row kernels), rotates q and
+k at each sequence's position and appends k and v in one ``ops.rope_append`` launch, and
+attends with ``ops.attn_decode``, which reads every K and V row once per KV head instead of
+once per query head and whose result for a sequence has the same bits in any batch. The
+lengths live on the device: a step has no host round trip.
 """
 
 from __future__ import annotations
@@ -326,9 +339,53 @@ def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool =
     return F.silu(_linear(h, wg, tiled, act)) * _linear(h, wu, tiled, act)
 
 
+def _rope_tables(capacity: int, d: int, theta: float, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """cos and sin [capacity, d] of `_rope` for positions 0 .. capacity - 1: the same
+    expressions on the same device, so row t holds the bits `_rope` uses at position t."""
+    inv = 1.0 / (theta ** (torch.arange(0, d, 2, device=device, dtype=torch.float32) / d))
+    pos = torch.arange(capacity, device=device, dtype=torch.float32)
+    ang = torch.outer(pos, inv)
+    return torch.cat([ang, ang], -1).cos(), torch.cat([ang, ang], -1).sin()
+
+
+@dataclass
+class KVCache:
+    """One layer's KV cache for `decoder_step`: `k` and `v` bf16 [batch, kv_heads,
+    capacity, head_dim] (k rotated), `lens` int32 [batch] on their device - positions
+    [0, lens[b]) of sequence b are valid, whatever lies behind is never read - the
+    rotary tables `cos`, `sin` f32 [capacity, head_dim], and `max_len`, a host upper
+    bound of `lens` that sizes the attention's grid without a device round trip."""
+    k: torch.Tensor
+    v: torch.Tensor
+    lens: torch.Tensor
+    cos: torch.Tensor
+    sin: torch.Tensor
+    capacity: int
+    max_len: int = 0
+
+    @classmethod
+    def allocate(cls, spec: DecoderSpec, batch: int, capacity: int, device="cpu",
+                 lens: Optional[torch.Tensor] = None) -> "KVCache":
+        """An empty cache: K and V uninitialised, lengths zero. `lens` (int32 [batch] on
+        `device`) lets the layers of a model share one length tensor."""
+        if batch < 1 or capacity < 1:
+            raise ValueError("batch and capacity must be positive")
+        device = torch.device(device)
+        if lens is None:
+            lens = torch.zeros(batch, dtype=torch.int32, device=device)
+        elif lens.dtype != torch.int32 or tuple(lens.shape) != (batch,) or lens.device.type != device.type:
+            raise ValueError(f"lens must be an int32 [{batch}] tensor on {device}")
+        shape = (batch, spec.kv_heads, capacity, spec.head_dim)
+        cos, sin = _rope_tables(capacity, spec.head_dim, spec.rope_theta, device)
+        return cls(torch.empty(shape, dtype=torch.bfloat16, device=device),
+                   torch.empty(shape, dtype=torch.bfloat16, device=device), lens, cos, sin, capacity, 0)
+
+
 def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True,
-                    fuse_gated: bool = False, tiled: bool = False, act: Optional[str] = None) -> torch.Tensor:
-    """One decoder layer on x [batch, seq, hidden] (causal self-attention, no KV cache).
+                    fuse_gated: bool = False, tiled: bool = False, act: Optional[str] = None,
+                    cache: Optional[KVCache] = None) -> torch.Tensor:
+    """One decoder layer on x [batch, seq, hidden] (causal self-attention; with `cache`
+    the prefill of a KV cache, see the end).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
     packed bytes (ops.mxfp4_linear, ops.mxfp6_linear or ops.fp8_linear), a packed norm
     weight is dequantized once. With `fuse`, MXFP4 gate and up projections run as one
@@ -350,21 +407,81 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     for any batch * seq with `fuse`. The result is that of the quantized activations,
     not of the W4A16 routes. A packed projection of another format raises ValueError
     instead of silently running W.A16; plain tensors are untouched; any other `act`
-    raises ValueError."""
+    raises ValueError.
+    `cache` (opt-in): the pass is the prefill of that `KVCache` - the rotated k and the
+    v of all seq positions are also stored at positions [0, seq) of every sequence,
+    `cache.lens` becomes seq everywhere and `cache.max_len` seq; `decoder_step` goes on
+    from there. The result is the same with and without it."""
     if act not in (None, "mxfp8"):
         raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
+    if cache is not None:
+        _check_cache(cache, spec, b, x.device)
+        if s > cache.capacity:
+            raise ValueError(f"{s} positions do not fit a cache of {cache.capacity}")
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
     q, k, v = _qkv(h, p, fuse, tiled, act)
     q = q.view(b, s, nh, hd).transpose(1, 2)
     k = k.view(b, s, nkv, hd).transpose(1, 2)
     v = v.view(b, s, nkv, hd).transpose(1, 2)
     q, k = _rope(q, spec.rope_theta), _rope(k, spec.rope_theta)
+    if cache is not None:
+        cache.k[:, :, :s] = k
+        cache.v[:, :, :s] = v
+        cache.lens.fill_(s)
+        cache.max_len = s
     k = k.repeat_interleave(nh // nkv, dim=1)
     v = v.repeat_interleave(nh // nkv, dim=1)
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
     x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"], tiled, act)
     h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
     return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled, act), p["down_proj"], tiled,
+                       act)
+
+
+def _check_cache(cache: KVCache, spec: DecoderSpec, batch: int, device: torch.device) -> None:
+    want = (batch, spec.kv_heads, cache.capacity, spec.head_dim)
+    if tuple(cache.k.shape) != want or tuple(cache.v.shape) != want:
+        raise ValueError(f"the cache holds k {tuple(cache.k.shape)} and v {tuple(cache.v.shape)}, "
+                         f"this batch and spec need {want}")
+    if cache.k.device != device:
+        raise ValueError(f"the cache is on {cache.k.device}, x on {device}")
+
+
+def decoder_step(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, cache: KVCache, fuse: bool = True,
+                 fuse_gated: bool = False, act: Optional[str] = None, advance: bool = True) -> torch.Tensor:
+    """One decode step of a decoder layer: x [batch, 1, hidden] is the new token of every
+    sequence, `cache` holds the k and v of the lens[b] tokens before it (a prefill by
+    ``decoder_forward(..., cache=cache)`` or earlier steps). The layer is `decoder_forward`'s
+    - the same norms, `_qkv`, `_linear` and `_gated`, so plain tensors, every packed route,
+    `fuse`, `fuse_gated` and `act="mxfp8"` mean what they mean there - with the attention
+    done against the cache: ``ops.rope_append`` rotates q and k at position lens[b] and
+    appends k and v, ``ops.attn_decode`` attends over the lens[b] + 1 positions, reading K
+    and V once per KV head. Nothing is read back to the host: the lengths stay on the
+    device and `cache.max_len` sizes the launch.
+    `advance` adds 1 to `cache.lens` (on the device) and to `cache.max_len`; with
+    advance=False the caller does both once for all layers that share `lens`.
+    ValueError for seq != 1, a batch or spec other than the cache's, and a full cache
+    (`max_len` == `capacity`)."""
+    if act not in (None, "mxfp8"):
+        raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
+    if x.dim() != 3 or x.shape[1] != 1:
+        raise ValueError(f"decoder_step takes x [batch, 1, hidden], got {tuple(x.shape)}")
+    b = x.shape[0]
+    _check_cache(cache, spec, b, x.device)
+    if cache.max_len >= cache.capacity:
+        raise ValueError(f"the cache is full: {cache.max_len} of {cache.capacity} positions")
+    from ..ops import attn_decode, rope_append
+
+    h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
+    q, k, v = _qkv(h, p, fuse, False, act)
+    q = rope_append(q, k, v, cache.cos, cache.sin, cache.k, cache.v, cache.lens)
+    a = attn_decode(q, cache.k, cache.v, cache.lens + 1, max_len=cache.max_len + 1, out_dtype=x.dtype)
+    if advance:
+        cache.lens.add_(1)
+        cache.max_len += 1
+    x = x + _linear(a.view(b, 1, spec.heads * spec.head_dim), p["o_proj"], False, act)
+    h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
+    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, False, act), p["down_proj"], False,
                        act)

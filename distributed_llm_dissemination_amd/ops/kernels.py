@@ -2,7 +2,8 @@
 
 Every op takes and returns CUDA (HIP) tensors (the consumers of a packed
 layer, mxfp4_unpack_range, mxfp4_linear, mxfp4_swiglu, fp8_unpack_range,
-fp8_linear, fp8_swiglu, mxfp6_unpack_range, mxfp6_linear and mxfp6_swiglu, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
+fp8_linear, fp8_swiglu, mxfp6_unpack_range, mxfp6_linear and mxfp6_swiglu, and the two ops of a decode step
+against a KV cache, rope_append and attn_decode, also take CPU tensors and then use the host reference) and runs on the caller's current stream, so it composes with PyTorch work without extra synchronization. Shapes,
 dtypes, alignment and sizes are checked on the host before any launch (a kernel
 must never be handed a buffer smaller than its grid assumes).
 
@@ -26,6 +27,9 @@ must never be handed a buffer smaller than its grid assumes).
     y6 = ops.mxfp6_linear(h, p6, 4096, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20) # h @ w.T from those bytes
     z6 = ops.mxfp6_swiglu(h, p6, 2048, 4096, src_bytes=2 * x.numel(), chunk_bytes=64 << 20, # the gated front half from
                           gate_offset=0, up_offset=2048 * 4096)                             # those bytes (fp8_swiglu: p8)
+    # one decode step's attention: caches bf16 [B, kv_heads, capacity, d], lens / pos int32 [B] on the device
+    q_rot = ops.rope_append(q, k, v, cos, sin, k_cache, v_cache, pos)     # rotate q and k at pos, append k and v
+    a = ops.attn_decode(q_rot, k_cache, v_cache, pos + 1)                 # [B, heads * d], K and V read once per KV head
 
 These are the kernels the data engine runs itself (staging-time fp8 packing,
 per-chunk CRC verification of every landed chunk); here they are usable on
@@ -71,6 +75,8 @@ __all__ = [
     "fp8_linear",
     "mxfp6_swiglu",
     "fp8_swiglu",
+    "rope_append",
+    "attn_decode",
 ]
 
 _FP8_BLOCKS = (32, 64, 128, 256, 512)
@@ -1113,3 +1119,170 @@ def fp8_swiglu(x: torch.Tensor, packed: torch.Tensor, out_features: int, in_feat
     gated kernel."""
     return _packed_swiglu("fp8", x, packed, out_features, in_features, src_bytes, chunk_bytes, block, gate_offset,
                           up_offset, out_dtype, split_k, row_tiles, out, tiled)
+
+
+_ATTN_D = (32, 64, 128)
+_ATTN_MAX_CAPACITY = 1 << 20
+
+
+def _check_caches(k_cache: torch.Tensor, v_cache: torch.Tensor) -> Tuple[int, int, int, int]:
+    """(B, kv_heads, capacity, d) of a pair of KV caches, checked."""
+    for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if c.dtype != torch.bfloat16:
+            raise ValueError(f"{name} must be {torch.bfloat16}, got {c.dtype}")
+        if c.dim() != 4 or c.numel() == 0:
+            raise ValueError(f"{name} must be [B, kv_heads, capacity, d], got {tuple(c.shape)}")
+        if not c.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if c.is_cuda and c.data_ptr() % 16:
+            raise ValueError(f"{name} must be 16-byte aligned")
+    if k_cache.shape != v_cache.shape or k_cache.device != v_cache.device:
+        raise ValueError("k_cache and v_cache must have one shape and one device")
+    b, kvh, cap, d = k_cache.shape
+    if d not in _ATTN_D:
+        raise ValueError(f"head_dim must be one of {_ATTN_D}, got {d}")
+    if cap > _ATTN_MAX_CAPACITY:
+        raise ValueError(f"capacity must be at most {_ATTN_MAX_CAPACITY} positions, got {cap}")
+    return b, kvh, cap, d
+
+
+def _check_index(t: torch.Tensor, name: str, b: int, device: torch.device) -> None:
+    if t.dtype != torch.int32:
+        raise ValueError(f"{name} must be {torch.int32}, got {t.dtype}")
+    if tuple(t.shape) != (b,) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [{b}] tensor, got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{name} must be on the caches' device")
+
+
+def _rows(t: torch.Tensor, name: str, b: int, n: int, device: torch.device) -> torch.Tensor:
+    """`t` as bf16 rows [b, n] with unit stride along the row and any row stride: the view
+    itself where it allows that (a last-dimension slice of a merged projection), else a copy."""
+    if t.dtype != torch.bfloat16:
+        raise ValueError(f"{name} must be {torch.bfloat16}, got {t.dtype}")
+    if t.device != device:
+        raise ValueError(f"{name} must be on the caches' device")
+    if t.numel() != b * n or t.dim() < 1 or t.shape[-1] != n:
+        raise ValueError(f"{name} must be [{b}, ..., {n}] with {b} rows, got {tuple(t.shape)}")
+    lead = [i for i in range(t.dim() - 1) if t.shape[i] != 1]
+    if t.stride(-1) == 1 and len(lead) <= 1:
+        ld = t.stride(lead[0]) if lead else n
+        if ld >= n:
+            return t.as_strided((b, n), (ld, 1))
+    return t.reshape(b, n).contiguous()
+
+
+def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+                k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+    """The rotary embedding of one new token per sequence, fused with the cache append.
+
+    `q` [B, ..., heads * d], `k` and `v` [B, ..., kv_heads * d] are bf16 rows of B sequences
+    (unit stride along the row, any row stride: the three last-dimension slices of one merged
+    q/k/v projection are used where they lie, as are three separate tensors); `k_cache` and
+    `v_cache` bf16 [B, kv_heads, capacity, d], contiguous, d 32, 64 or 128; `cos`, `sin` f32
+    [capacity, d], the tables of the rotate-half rotary embedding; `pos` int32 [B] on the
+    caches' device. Returns q rotated at `pos`, bf16 [B, heads, d], and writes k rotated at
+    `pos` and v as it is to position pos[b] of every KV head of sequence b. The rotation is
+    ``x * cos + rot(x) * sin`` in f32 - two rounded products, one rounded sum, no FMA - rounded
+    once to bf16: the bits plain torch gives for the same expression. A pos[b] outside
+    [0, capacity) writes nothing to the caches and gives a zero q row.
+    GPU: one launch on the current stream, no synchronization (`pos` is never read on the
+    host). CPU: plain torch."""
+    b, kvh, cap, d = _check_caches(k_cache, v_cache)
+    dev = k_cache.device
+    _check_index(pos, "pos", b, dev)
+    for name, t in (("cos", cos), ("sin", sin)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (cap, d) or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous f32 [{cap}, {d}] tensor on the caches' device")
+    if q.dim() < 1 or q.shape[-1] <= 0 or q.shape[-1] % d:
+        raise ValueError(f"q must be [B, ..., heads * {d}], got {tuple(q.shape)}")
+    heads = q.shape[-1] // d
+    if heads % kvh:
+        raise ValueError(f"heads ({heads}) must be a multiple of kv_heads ({kvh})")
+    if heads + 2 * kvh > 65535:
+        raise ValueError("heads + 2 * kv_heads must fit a grid dimension (65535)")
+    q2, k2, v2 = _rows(q, "q", b, heads * d, dev), _rows(k, "k", b, kvh * d, dev), _rows(v, "v", b, kvh * d, dev)
+    if not dev.type == "cuda":
+        ok = (pos >= 0) & (pos < cap)
+        p = pos.clamp(0, cap - 1).long()
+        c, s = cos[p][:, None, :], sin[p][:, None, :]  # [B, 1, d]
+
+        def rot(x, nh):
+            x = x.reshape(b, nh, d).float()
+            return (x * c + torch.cat([-x[..., d // 2:], x[..., : d // 2]], -1) * s).to(torch.bfloat16)
+
+        q_out = torch.where(ok[:, None, None], rot(q2, heads), torch.zeros((), dtype=torch.bfloat16))
+        rows = ok.nonzero().flatten()
+        k_cache[rows, :, p[rows]] = rot(k2, kvh)[rows]
+        v_cache[rows, :, p[rows]] = v2.reshape(b, kvh, d)[rows]
+        return q_out
+    q_out = torch.empty(b, heads, d, dtype=torch.bfloat16, device=dev)
+    _core.attn_rope_append(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(), v2.stride(0),
+                           pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), b, heads, kvh, d, cap, q_out.data_ptr(),
+                           k_cache.data_ptr(), v_cache.data_ptr(), _stream())
+    return q_out
+
+
+def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor, *,
+                max_len: Optional[int] = None, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """Grouped-query attention of one query token per sequence against a KV cache:
+    row b of the [B, heads * d] result is, per head h, ``softmax(q[b, h] @ K.T / sqrt(d)) @ V``
+    over K, V = cache[b, h // (heads // kv_heads), :lens[b]].
+
+    `q` bf16 [B, heads, d]; the caches bf16 [B, kv_heads, capacity, d], contiguous, d 32, 64
+    or 128, capacity at most 2**20, heads // kv_heads in 1..16; `lens` int32 [B] on the
+    caches' device, 0 <= lens[b] <= `max_len`, a host upper bound that sizes the grid and the
+    workspace (default: the capacity - a decode loop that knows its lengths should pass it).
+    Positions at or behind lens[b] are never read - the cache there may hold anything - and
+    lens[b] == 0 gives a zero row. `out_dtype` bf16 or f32; the bf16 result is the f32 one
+    rounded to nearest even.
+    GPU (attn_decode.hip): a workgroup serves one (sequence, KV head, chunk of
+    `_core.attn_decode_chunk()` positions) and all the query heads of the KV head, so K and V
+    are read once per KV head; f32 scores and online softmax, P rounded to bf16 for P @ V on
+    the bf16 MFMA; f32 chunk partials in a workspace, merged in ascending chunk order by a
+    second launch. Chunk boundaries are multiples of the constant, so a sequence's row has the
+    same bits in any batch, at any slot, under any capacity and `max_len`. Two launches on the
+    current stream, no synchronization, no atomics. CPU: per sequence the definition in f32."""
+    b, kvh, cap, d = _check_caches(k_cache, v_cache)
+    dev = k_cache.device
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    if q.dtype != torch.bfloat16:
+        raise ValueError(f"q must be {torch.bfloat16}, got {q.dtype}")
+    if q.device != dev:
+        raise ValueError("q must be on the caches' device")
+    if q.dim() != 3 or q.shape[0] != b or q.shape[2] != d or q.shape[1] < 1:
+        raise ValueError(f"q must be [{b}, heads, {d}], got {tuple(q.shape)}")
+    heads = q.shape[1]
+    if heads % kvh:
+        raise ValueError(f"heads ({heads}) must be a multiple of kv_heads ({kvh})")
+    if heads // kvh > 16:
+        raise ValueError(f"at most 16 query heads per KV head, got {heads // kvh}")
+    _check_index(lens, "lens", b, dev)
+    max_len = cap if max_len is None else int(max_len)
+    if not 1 <= max_len <= cap:
+        raise ValueError(f"max_len must be in 1..capacity ({cap}), got {max_len}")
+    if dev.type != "cuda":
+        y = torch.zeros(b, heads, d, dtype=torch.float32)
+        g = heads // kvh
+        for i, n in enumerate(lens.tolist()):
+            n = min(max(n, 0), cap)
+            if n == 0:
+                continue
+            kk = k_cache[i, :, :n].float().repeat_interleave(g, dim=0)  # [heads, n, d]
+            vv = v_cache[i, :, :n].float().repeat_interleave(g, dim=0)
+            s = torch.einsum("hd,hnd->hn", q[i].float(), kk) / d ** 0.5
+            y[i] = torch.einsum("hn,hnd->hd", torch.softmax(s, -1), vv)
+        return y.view(b, heads * d).to(out_dtype)
+    if not q.is_contiguous():
+        q = q.contiguous()
+    if q.data_ptr() % 16:
+        q = q.clone()
+    nbytes = _core.attn_decode_workspace_bytes(b, heads, kvh, d, cap, max_len)
+    if nbytes < 0 or b * heads > 0x7FFFFFFF:
+        raise ValueError("the batch is too large for one launch")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    y = torch.empty(b, heads * d, dtype=out_dtype, device=dev)
+    _core.attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr(), b, heads, kvh, d, cap,
+                      max_len, ws.data_ptr(), nbytes, y.data_ptr(), out_dtype == torch.bfloat16, _stream())
+    return y
