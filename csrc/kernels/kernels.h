@@ -294,10 +294,21 @@ hipError_t fp8_swiglu_tiled(const void* packed, int64_t src_bytes, int64_t src_c
 // attn_decode: y[b, h * d ...] = softmax(q[b, h] . K[b, h / group, :lens[b]] /
 // sqrt(d)) V[b, h / group, :lens[b]] for q bf16 [B, heads, d] (contiguous, 16-B
 // aligned), lens int32 [B] on the device with 0 <= lens[b] <= max_len <=
-// capacity (a larger lens[b] is clamped to the capacity and never reads out of
-// bounds, but its row is then unspecified), group = heads / kv_heads in 1..16; y
-// is [B, heads * d] f32 or bf16 (the f32 result rounded to nearest even).
-// lens[b] = 0 gives a zero row. A workgroup serves one (b, KV head, chunk of
+// capacity, group = heads / kv_heads in 1..16; y is [B, heads * d] f32 or bf16
+// (the f32 result rounded to nearest even). lens[b] = 0 gives a zero row.
+// Outside that promise both kernels clamp lens[b] to [0, capacity]: a negative
+// one is a zero row, one above the capacity the row of the capacity; above
+// max_len the row is that of the positions below lens[b] in the chunks that
+// cover max_len (the combine kernel stops at the workspace's last chunk). No
+// load leaves the caches, no store the workspace, and no other sequence's row
+// changes. Finite scores of any size are exact in the softmax (an underflowed
+// weight is exactly 0); bf16-subnormal V and f32-subnormal products are not
+// flushed. Inside the valid prefix a NaN in a K row makes the rows of that (b,
+// KV head)'s query heads NaN, +inf in a V element makes that d of those heads
+// +inf where the position has weight and NaN (0 * inf) where its weight
+// underflowed to 0; a head with a score that overflows f32 to +inf is NaN; the
+// numerator sum(p~ v), p~ <= 1, is f32 and gives +-inf where it overflows
+// before the division. Every other element keeps its bits. A workgroup serves one (b, KV head, chunk of
 // kAttnDecodeChunk positions) and the KV head's whole group, so K and V rows are
 // read once per KV head; scores and the online softmax are f32, P is rounded to
 // bf16 for P V on v_mfma_f32_16x16x32_bf16; chunk partials (m, l, o) are f32 in

@@ -1242,7 +1242,21 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     the bf16 MFMA; f32 chunk partials in a workspace, merged in ascending chunk order by a
     second launch. Chunk boundaries are multiples of the constant, so a sequence's row has the
     same bits in any batch, at any slot, under any capacity and `max_len`. Two launches on the
-    current stream, no synchronization, no atomics. CPU: per sequence the definition in f32."""
+    current stream, no synchronization, no atomics. CPU: per sequence the definition in f32.
+    `lens` outside the promise: a negative lens[b] is 0 (a zero row), one above the capacity is
+    the capacity; a lens[b] above `max_len` gives a finite row of finite cache rows (GPU: the
+    positions below lens[b] of the chunks that cover `max_len`) and never reads outside the
+    caches or the workspace. No other sequence's row changes by a bit in any of these cases.
+    Magnitudes, on the GPU: finite scores of any size are exact in the softmax (a weight that
+    underflows is exactly 0), bf16-subnormal V and f32-subnormal products are kept, not
+    flushed. Non-finite values inside the valid prefix stay with the query heads of their
+    (sequence, KV head) and leave every other element its bits: a NaN in a K row makes those
+    heads' rows NaN; +inf in a V element makes that d of those heads +inf where the position
+    has weight, and NaN where its weight underflowed to 0 (0 * inf; the definition gives
+    +inf). A head one of whose scores q . k overflows f32 to +inf gets a NaN row (the
+    definition: the V row of that position). The numerator sum(p~ v), p~ = exp(s - max s) <=
+    1, is summed in f32 before the division by sum(p~): where it overflows the result is +-inf
+    although the quotient would be finite."""
     b, kvh, cap, d = _check_caches(k_cache, v_cache)
     dev = k_cache.device
     if out_dtype not in (torch.bfloat16, torch.float32):
