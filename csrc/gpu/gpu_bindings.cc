@@ -36,6 +36,17 @@ void check(hipError_t e, const char* what) {
 
 hipStream_t as_stream(uint64_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// (mt, nt or pairs, slices) of one pass of a decode launcher (kernels.h, DecodePlan); host code only.
+template <kern::DecodePlan (*Plan)(int, int64_t, int64_t, int, int)>
+py::tuple decode_plan(int m, int64_t n, int64_t k, int split_k, int row_tiles) {
+  if (m < 1 || m > 64 || n < 16 || n % 16 || k < 32 || k % 32 || split_k < 0 || split_k > 16 ||
+      (row_tiles != 0 && row_tiles != 1 && row_tiles != 2 && row_tiles != 4) || (row_tiles && n / 16 % row_tiles))
+    throw std::invalid_argument("decode plan: m in 1..64, n a multiple of 16, k of 32, split_k in 0..16, row_tiles "
+                                "0, 1, 2 or 4 and a divisor of n / 16");
+  const kern::DecodePlan p = Plan(m, n, k, split_k, row_tiles);
+  return py::make_tuple(p.mt, p.nt, p.slices);
+}
+
 // Per-device scratch for synchronous CRC calls from Python.
 struct Scratch {
   void* ws = nullptr;
@@ -554,6 +565,8 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"), py::arg("split_k") = 0,
      py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("mxfp4_linear_slices", &kern::mxfp4_linear_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  m.def("mxfp4_linear_plan", &decode_plan<kern::mxfp4_linear_plan>, py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("split_k") = 0, py::arg("row_tiles") = 0);
   // silu(x Wg^T) * (x Wu^T) from two parameters of the packed layer (kernels/mxfp4_swiglu.hip); stream-ordered
   m.def("mxfp4_swiglu", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
                            uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
@@ -566,6 +579,8 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
      py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("mxfp4_swiglu_slices", &kern::mxfp4_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  m.def("mxfp4_swiglu_plan", &decode_plan<kern::mxfp4_swiglu_plan>, py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("split_k") = 0, py::arg("row_tiles") = 0);
   // the same two for many rows of x, one launch for any m (kernels/mxfp4_tiled.hip); stream-ordered
   m.def("mxfp4_linear_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,
                                  int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
@@ -630,6 +645,8 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
      py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("fp8_linear_slices", &kern::fp8_linear_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  m.def("fp8_linear_plan", &decode_plan<kern::fp8_linear_plan>, py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("split_k") = 0, py::arg("row_tiles") = 0);
   // W6A16 linear from the MXFP6-packed layer in place (kernels/mxfp6_linear.hip); stream-ordered
   m.def("mxfp6_linear", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,
                            int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16, int split_k,
@@ -642,6 +659,8 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"), py::arg("split_k") = 0,
      py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("mxfp6_linear_slices", &kern::mxfp6_linear_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  m.def("mxfp6_linear_plan", &decode_plan<kern::mxfp6_linear_plan>, py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("split_k") = 0, py::arg("row_tiles") = 0);
   // silu(x Wg^T) * (x Wu^T) from two parameters of the MXFP6-packed layer (kernels/mxfp6_swiglu.hip); stream-ordered
   m.def("mxfp6_swiglu", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
                            uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy, bool y_bf16,
@@ -654,6 +673,8 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"), py::arg("y_bf16"),
      py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("mxfp6_swiglu_slices", &kern::mxfp6_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  m.def("mxfp6_swiglu_plan", &decode_plan<kern::mxfp6_swiglu_plan>, py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("split_k") = 0, py::arg("row_tiles") = 0);
   // the same from the fp8-packed layer (kernels/fp8_swiglu.hip); stream-ordered
   m.def("fp8_swiglu", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t gate_off,
                          int64_t up_off, uint64_t x, int64_t m_rows, int64_t n, int64_t k, uint64_t y, int64_t ldy,
@@ -666,6 +687,8 @@ void register_gpu_bindings(PyObject* module) {
      py::arg("up_off"), py::arg("x"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("y"), py::arg("ldy"),
      py::arg("y_bf16"), py::arg("split_k") = 0, py::arg("row_tiles") = 0, py::arg("stream") = 0);
   m.def("fp8_swiglu_slices", &kern::fp8_swiglu_slices, py::arg("m"), py::arg("n"), py::arg("k"));
+  m.def("fp8_swiglu_plan", &decode_plan<kern::fp8_swiglu_plan>, py::arg("m"), py::arg("n"), py::arg("k"),
+        py::arg("split_k") = 0, py::arg("row_tiles") = 0);
   // the MXFP6 and fp8 pairs for many rows of x, one launch for any m (kernels/mxfp6_tiled.hip,
   // kernels/fp8_tiled.hip); stream-ordered
   m.def("mxfp6_linear_tiled", [](uint64_t packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, uint64_t x,

@@ -228,10 +228,20 @@ int auto_slices(int m, int mt, int nt, int64_t wgs, int64_t nsteps) {
 
 }  // namespace
 
+// One pass of m rows: the instantiation and the K slices, the only place the launcher below takes them from
+// (kernels.h, DecodePlan).
+DecodePlan fp8_linear_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave) {
+  if (m < 1 || m > 64) return DecodePlan{0, 0, 0};
+  const int rt = row_tiles_per_wave;
+  const int mt = (m + 15) / 16;
+  const int nt = rt ? std::min(rt, mt <= 2 ? 4 : 2) : row_tiles(m, mt, N / 16);
+  const int64_t wgs = N / 16 / nt;
+  const int slices = std::min(split_k ? split_k : auto_slices(m, mt, nt, wgs, K / 128), max_slices(mt, nt));
+  return DecodePlan{mt, nt, slices};
+}
+
 int fp8_linear_slices(int64_t M, int64_t N, int64_t K) {
-  const int m = int(std::min<int64_t>(M, 64)), mt = (m + 15) / 16;
-  const int nt = row_tiles(m, mt, N / 16);
-  return auto_slices(m, mt, nt, N / 16 / nt, K / 128);
+  return fp8_linear_plan(int(std::min<int64_t>(M, 64)), N, K, 0, 0).slices;
 }
 
 hipError_t fp8_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
@@ -260,10 +270,9 @@ hipError_t fp8_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, 
   const size_t ysz = y_bf16 ? 2 : 4;
   for (int64_t m0 = 0; m0 < M; m0 += 64) {
     const int m = int(std::min<int64_t>(64, M - m0));
-    const int mt = (m + 15) / 16;
-    const int nt = rt ? std::min(rt, mt <= 2 ? 4 : 2) : row_tiles(m, mt, N / 16);
+    const DecodePlan plan = fp8_linear_plan(m, N, K, split_k, rt);
+    const int mt = plan.mt, nt = plan.nt, slices = plan.slices;
     const int64_t wgs = N / 16 / nt;
-    const int slices = std::min(split_k ? split_k : auto_slices(m, mt, nt, wgs, K / 128), max_slices(mt, nt));
     const dim3 grid{unsigned(wgs)}, blk{unsigned(64 * slices)};
     const size_t lds = slices > 1 ? size_t(slices) * mt * nt * 256 * sizeof(float) : 0;
     const uint16_t* xp = x + m0 * K;

@@ -129,7 +129,19 @@ hipError_t mxfp6_verify_unpack_batch(const FusedItem* items, int n, void* worksp
 // chosen from the shape; 1, 2 or 4, a divisor of N / 16; at most 2 beyond 32
 // rows of x): the 16-row tiles of W a wave feeds from one x fragment. Rows of x
 // beyond 64 are served by further passes over W.
+//
+// DecodePlan is the template instantiation and workgroup size one pass of a
+// decode launcher runs: `mt` 16-row tiles of x, `nt` row tiles (gated kernels:
+// pairs) per wave, `slices` waves over K. Every *_plan(m, N, K, split_k,
+// row_tiles_per_wave) below is the one place its launcher takes these from, for
+// a pass of m rows (1..64; anything else: {0, 0, 0}), after clipping a forced
+// row_tiles_per_wave to what mt allows and slices to what registers and LDS
+// hold. *_slices(M, N, K) is plan(min(M, 64), N, K, 0, 0).slices.
+struct DecodePlan {
+  int mt, nt, slices;
+};
 int mxfp4_linear_slices(int64_t M, int64_t N, int64_t K);
+DecodePlan mxfp4_linear_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave);
 hipError_t mxfp4_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, const uint16_t* x,
                         int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
                         int row_tiles_per_wave, hipStream_t s);
@@ -146,6 +158,7 @@ hipError_t mxfp4_linear(const void* packed, int64_t src_bytes, int64_t src_chunk
 // gate and an up tile: 0 = chosen, 1 or 2 (a divisor of N / 16; 1 beyond 32
 // rows of x). Stream-ordered, no allocation, no workspace, no atomics.
 int mxfp4_swiglu_slices(int64_t M, int64_t N, int64_t K);
+DecodePlan mxfp4_swiglu_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave);
 hipError_t mxfp4_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
                         const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
                         int split_k, int row_tiles_per_wave, hipStream_t s);
@@ -210,6 +223,7 @@ hipError_t mxfp4_swiglu_mx(const void* packed, int64_t src_bytes, int64_t src_ch
 // n + 4 n / block bytes, then starts 16-B aligned); `src_bytes` a multiple of
 // 2 * block; `packed` 16-B aligned. Anything else: hipErrorInvalidValue.
 int fp8_linear_slices(int64_t M, int64_t N, int64_t K);
+DecodePlan fp8_linear_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave);
 hipError_t fp8_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t elem_off,
                       const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
                       int split_k, int row_tiles_per_wave, hipStream_t s);
@@ -225,6 +239,7 @@ hipError_t fp8_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, 
 // aligned), `src_bytes` a positive multiple of 64 and `packed` 16-B aligned.
 // Anything else: hipErrorInvalidValue.
 int mxfp6_linear_slices(int64_t M, int64_t N, int64_t K);
+DecodePlan mxfp6_linear_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave);
 hipError_t mxfp6_linear(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t elem_off, const uint16_t* x,
                         int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16, int split_k,
                         int row_tiles_per_wave, hipStream_t s);
@@ -240,10 +255,12 @@ hipError_t mxfp6_linear(const void* packed, int64_t src_bytes, int64_t src_chunk
 // chosen, 1 or 2, a divisor of N / 16; 1 beyond 32 rows of x), stream order, no
 // allocation, no workspace, no atomics: as for mxfp4_swiglu.
 int mxfp6_swiglu_slices(int64_t M, int64_t N, int64_t K);
+DecodePlan mxfp6_swiglu_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave);
 hipError_t mxfp6_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
                         const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy, bool y_bf16,
                         int split_k, int row_tiles_per_wave, hipStream_t s);
 int fp8_swiglu_slices(int64_t M, int64_t N, int64_t K);
+DecodePlan fp8_swiglu_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave);
 hipError_t fp8_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int block, int64_t gate_off,
                       int64_t up_off, const uint16_t* x, int64_t M, int64_t N, int64_t K, void* y, int64_t ldy,
                       bool y_bf16, int split_k, int row_tiles_per_wave, hipStream_t s);

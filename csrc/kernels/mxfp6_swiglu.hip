@@ -249,11 +249,20 @@ bool param_ok(int64_t off, int64_t src_bytes, int64_t N, int64_t K) {
 
 }  // namespace
 
+// One pass of m rows: the instantiation and the K slices, the only place the launcher below takes them from
+// (kernels.h, DecodePlan).
+DecodePlan mxfp6_swiglu_plan(int m, int64_t N, int64_t K, int split_k, int row_tiles_per_wave) {
+  if (m < 1 || m > 64) return DecodePlan{0, 0, 0};
+  const int rt = row_tiles_per_wave;
+  const int mt = (m + 15) / 16;
+  const int p = rt ? std::min(rt, mt <= 2 ? 2 : 1) : pairs(m, mt, N / 16);
+  const int64_t wgs = N / 16 / p;
+  const int slices = std::min(split_k ? split_k : auto_slices(m, mt, p, wgs, K / 128), max_slices(mt, p));
+  return DecodePlan{mt, p, slices};
+}
+
 int mxfp6_swiglu_slices(int64_t M, int64_t N, int64_t K) {
-  const int mt = int(std::min<int64_t>(4, (M + 15) / 16));
-  const int m = int(std::min<int64_t>(M, 64));
-  const int p = pairs(m, mt, N / 16);
-  return auto_slices(m, mt, p, N / 16 / p, K / 128);
+  return mxfp6_swiglu_plan(int(std::min<int64_t>(M, 64)), N, K, 0, 0).slices;
 }
 
 hipError_t mxfp6_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk, int64_t gate_off, int64_t up_off,
@@ -274,10 +283,9 @@ hipError_t mxfp6_swiglu(const void* packed, int64_t src_bytes, int64_t src_chunk
   const size_t ysz = y_bf16 ? 2 : 4;
   for (int64_t m0 = 0; m0 < M; m0 += 64) {
     const int m = int(std::min<int64_t>(64, M - m0));
-    const int mt = (m + 15) / 16;
-    const int p = rt ? std::min(rt, mt <= 2 ? 2 : 1) : pairs(m, mt, N / 16);
+    const DecodePlan plan = mxfp6_swiglu_plan(m, N, K, split_k, rt);
+    const int mt = plan.mt, p = plan.nt, slices = plan.slices;
     const int64_t wgs = N / 16 / p;
-    const int slices = std::min(split_k ? split_k : auto_slices(m, mt, p, wgs, K / 128), max_slices(mt, p));
     const dim3 grid{unsigned(wgs)}, block{unsigned(64 * slices)};
     const size_t lds = slices > 1 ? size_t(slices) * mt * 2 * p * 256 * sizeof(float) : 0;
     const uint16_t* xp = x + m0 * K;
