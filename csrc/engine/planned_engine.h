@@ -466,6 +466,10 @@ class PlannedEngine : public DataEngine {
   std::deque<DiskRead> disk_todo_, disk_done_;
   std::vector<std::thread> readers_;
   int disk_inflight_ = 0;
+  // The kernel could not read with O_DIRECT into the pinned bounce buffers (EFAULT:
+  // their mapping gives it no pages to pin): readers then read into aligned
+  // memory of their own and copy into the bounce buffer.
+  std::atomic<bool> direct_via_host_{false};
   std::unique_ptr<NodePacer> pacer_;  // node-shared disk budget (node_disk_rate > 0)
 
   std::mutex stats_mu_;

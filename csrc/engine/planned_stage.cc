@@ -9,7 +9,9 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
+#include <cstdlib>
 #include <cstring>
 
 #include "core/fp8.h"
@@ -223,6 +225,7 @@ void PlannedEngine::pump_disk() {
 void PlannedEngine::reader_loop() {
   std::map<std::string, int> fds;
   std::map<std::string, bool> direct;  // path -> opened with O_DIRECT
+  uint8_t* aligned = nullptr;          // this reader's landing when direct_via_host_
   for (;;) {
     DiskRead d;
     {
@@ -252,13 +255,31 @@ void PlannedEngine::reader_loop() {
       std::lock_guard<std::mutex> lk(stats_mu_);
       stats_.disk_wait_ms += double(w) / 1e6;
     }
+    // Where the read lands: the bounce buffer, or - O_DIRECT where the kernel
+    // cannot pin the bounce buffer's pages - this reader's own aligned memory.
+    auto landing = [&]() -> uint8_t* {
+      if (!direct[d.path] || !direct_via_host_.load()) return d.bounce;
+      if (!aligned && posix_memalign(reinterpret_cast<void**>(&aligned), 4096, size_t(cfg_.chunk_bytes)) != 0)
+        aligned = nullptr;
+      return aligned;
+    };
+    uint8_t* dst = landing();
     int64_t got = 0;
-    while (fd >= 0 && got < d.len) {
-      ssize_t r = ::pread(fd, d.bounce + got, size_t(want - got), off_t(d.file_off + got));
+    while (fd >= 0 && dst && got < d.len) {
+      ssize_t r = ::pread(fd, dst + got, size_t(want - got), off_t(d.file_off + got));
+      if (r < 0 && errno == EFAULT && direct[d.path] && dst == d.bounce) {
+        if (!direct_via_host_.exchange(true))
+          log::warn(int64_t(self_node_)).s("path", d.path)
+              .msg("O_DIRECT cannot read into pinned memory here: reading into host memory and copying");
+        dst = landing();
+        got = 0;
+        continue;
+      }
       if (r <= 0) break;
       got += r;
     }
-    d.ok = got >= d.len;
+    d.ok = dst && got >= d.len;
+    if (d.ok && dst != d.bounce) memcpy(d.bounce, dst, size_t(d.len));
     {
       std::lock_guard<std::mutex> lk(stats_mu_);
       (direct[d.path] ? stats_.disk_direct_bytes : stats_.disk_buffered_bytes) += got;
@@ -271,6 +292,7 @@ void PlannedEngine::reader_loop() {
   }
   for (auto& kv : fds)
     if (kv.second > 0) ::close(kv.second);
+  ::free(aligned);
 }
 
 void PlannedEngine::stage_from(Layer& L, LayerID id, int64_t c, const uint8_t* src, uint8_t* bounce) {

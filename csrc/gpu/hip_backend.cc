@@ -5,7 +5,9 @@
 
 #include <chrono>
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
+#include <new>
 #include <thread>
 #include <map>
 #include <mutex>
@@ -586,7 +588,18 @@ hipStream_t create_stream_on_last(int device, int n) {
 
 std::shared_ptr<HostBuffer> alloc_pinned(int64_t size) {
   void* p = nullptr;
-  HIP_OK(hipHostMalloc(&p, size_t(std::max<int64_t>(size, 1)), hipHostMallocDefault));
+  const size_t n = size_t(std::max<int64_t>(size, 1));
+  const hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
+  if (e == hipErrorOutOfMemory) {
+    // The pinned pool is smaller than host memory on some machines (64 GiB of
+    // 300 on a virtual one): the layers past it live in pageable memory, which
+    // the runtime stages through pinned buffers of its own - slower, and said so.
+    (void)hipGetLastError();
+    if (posix_memalign(&p, 4096, n) != 0) throw std::bad_alloc();
+    log::warn(0).i("bytes", int64_t(n)).msg("pinned host memory exhausted: buffer is pageable, its copies are staged");
+    return HostBuffer::wrap(static_cast<uint8_t*>(p), size, std::shared_ptr<void>(p, ::free));
+  }
+  HIP_OK(e);
   return HostBuffer::wrap(static_cast<uint8_t*>(p), size,
                           std::shared_ptr<void>(p, [](void* q) { (void)hipHostFree(q); }));
 }
