@@ -80,7 +80,7 @@ bin/walkprobe: csrc/tools/walkprobe.hip
 
 bin/h2dbench: csrc/tools/h2dbench.hip
 	@mkdir -p bin
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $< -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -o $@ $< -L$(TORCHLIB) -Wl,-rpath,$(TORCHLIB) -lamdhip64 -lpthread
 
 bin/diskspeed: csrc/tools/diskspeed.cc
 	@mkdir -p bin

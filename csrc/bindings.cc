@@ -375,6 +375,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readonly("paced", &PlannedStats::paced)
       .def_readonly("disk_wait_ms", &PlannedStats::disk_wait_ms)
       .def_readonly("disk_direct_bytes", &PlannedStats::disk_direct_bytes)
+      .def_readonly("host_bounce_bytes", &PlannedStats::host_bounce_bytes)
       .def_readonly("scratch_landings", &PlannedStats::scratch_landings)
       .def_readonly("scratch_buffers", &PlannedStats::scratch_buffers)
       .def_readonly("disk_buffered_bytes", &PlannedStats::disk_buffered_bytes)
@@ -440,6 +441,7 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("link_bps", &SimTiming::link_bps)
       .def_readwrite("link", &SimTiming::link)
       .def_readwrite("stage_bps", &SimTiming::stage_bps)
+      .def_readwrite("host_copy_bps", &SimTiming::host_copy_bps)
       .def_readwrite("copy_bytes", &SimTiming::copy_bytes)
       .def_readwrite("p2p_rounds", &SimTiming::p2p_rounds)
       .def_readwrite("host", &SimTiming::host)
@@ -451,6 +453,11 @@ PYBIND11_MODULE(_core, m) {
       .def_readwrite("verify_bps", &SimTiming::verify_bps)
       .def_readwrite("verify_launch_s", &SimTiming::verify_launch_s);
   m.def("sim_set_timing", &sim_set_timing, py::arg("comm_key"), py::arg("timing"));
+  m.def("sim_set_pageable", [](const LayerSrc& s, bool on) {
+    if (!s.host) throw std::invalid_argument("sim_set_pageable: the layer has no host buffer");
+    sim_set_pageable(s.host->ptr, s.host->size, on);
+  }, py::arg("layer"), py::arg("on") = true,
+        "the simulator treats this layer's host buffer as pageable (on) or pinned again (off); process-wide");
   // Virtual clock (core/vclock.h): the simulator in model time. Python threads
   // that drive a session's ranks are counted by the clock between adopt() and
   // release() (reserve first, from the thread that starts them).

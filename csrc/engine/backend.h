@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -54,12 +55,26 @@ class Backend {
   // page-aligned host staging memory the copy queue can DMA from (pinned on GPUs)
   virtual uint8_t* alloc_host(int64_t n) = 0;
   virtual void free_host(uint8_t* p) = 0;
-  // copy queue: async host -> device copy; event fires when it landed
-  virtual Ev stage(uint8_t* dst, const uint8_t* src_host, int64_t n) = 0;
+  // Can the copy queues DMA straight from this host address (pinned or
+  // registered memory)? Pageable memory cannot: a copy from it blocks its
+  // caller while the runtime stages the bytes, so the engine moves such chunks
+  // through its bounce ring instead (planned_stage.cc).
+  virtual bool host_pinned(const uint8_t* p) {
+    (void)p;
+    return true;
+  }
+  // A reader thread's copy of a pageable chunk into a bounce buffer.
+  virtual void copy_host(uint8_t* dst, const uint8_t* src, int64_t n) { memcpy(dst, src, size_t(n)); }
+  // copy queue: async host -> device copy; event fires when it landed.
+  // `bounce`: the source is a bounce buffer filled from pageable host memory;
+  // the copy goes on a queue of its own, past whatever the other copy queues
+  // still hold, so the buffer returns to the ring at once.
+  virtual Ev stage(uint8_t* dst, const uint8_t* src_host, int64_t n, bool bounce = false) = 0;
   // copy queue: host -> device copy of `n_src` bytes of bf16, then pack them
   // into dst in the packed chunk layout of `format` (core/fp8.h with `block`
   // elements per scale, or core/mxfp4.h or core/mxfp6.h, whose block is 32)
-  virtual Ev stage_pack(uint8_t* dst, const uint8_t* src_host, int64_t n_src, int block, int format = kPackFp8) = 0;
+  virtual Ev stage_pack(uint8_t* dst, const uint8_t* src_host, int64_t n_src, int block, int format = kPackFp8,
+                        bool bounce = false) = 0;
   // Independent comm lanes (>= 1).
   virtual int lanes() const { return 1; }
   // comm lane `lane`: wait for `waits`, then one grouped set of P2P sends/recvs
@@ -208,7 +223,8 @@ struct SimFabricStats {
 struct SimTiming {
   double link_bps = 0;                            // every directed rank->rank link
   std::map<std::pair<int, int>, double> link;     // per directed link override
-  double stage_bps = 0;                           // host->device staging per rank (PCIe)
+  double stage_bps = 0;                           // host->device staging per rank (PCIe), shared by its copy queues
+  double host_copy_bps = 0;                       // a reader thread's copy of a pageable chunk into a bounce buffer
   bool copy_bytes = true;                         // false: move no payload bytes (timing-only runs)
   // Model RCCL's P2P schedule with few channels: a group's ops run in rounds of
   // one ring distance each (send to rank+d, recv from rank-d), round d+1 only
@@ -251,5 +267,8 @@ SimFabricStats sim_fabric_stats(const std::string& comm_key);
 void sim_clear_trace(const std::string& comm_key);
 // Set the timing model of a fabric (before its ranks start moving bytes).
 void sim_set_timing(const std::string& comm_key, const SimTiming& t);
+// Tests: SimBackend::host_pinned answers "pageable" for addresses inside a
+// range registered here (process-wide; `on` false removes the range again).
+void sim_set_pageable(const uint8_t* p, int64_t n, bool on);
 
 }  // namespace dissem

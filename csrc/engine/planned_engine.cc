@@ -104,6 +104,10 @@ PlannedEngine::PlannedEngine(const PlannedConfig& cfg, std::unique_ptr<Backend> 
   stats_.lane_connect_ms = backend_->lane_connect_ms();
   for (int r = 0; r < cfg_.world; ++r) node_rank_[cfg_.rank_nodes[size_t(r)]] = r;
   self_node_ = cfg_.rank_nodes[size_t(cfg_.rank)];
+  // The bounce ring now, not at its first use: an engine is built before its
+  // runtime allocates any layer, so the ring has its pinned memory even where
+  // the layers then use up the pool - the very case whose pageable layers need it.
+  alloc_ring();
   th_ = vclock::spawn([this] { run(); }, "engine-issue");
   monitor_ = vclock::spawn([this] { monitor_loop(); }, "engine-monitor");
 }
@@ -1053,6 +1057,7 @@ void PlannedEngine::take_requests(bool block) {
             L.fails[c] = 0;
           }
           L.host = nullptr;  // re-read the source from the next session's store
+          L.host_pinned = -1;
           L.host_prefix = -1;
           L.client_requested = false;
           L.stage_rate = -1;
@@ -1077,6 +1082,7 @@ void PlannedEngine::take_requests(bool block) {
         Layer& L = layer(r.layer);
         if (!L.size || !r.base) break;
         L.host = r.base;
+        L.host_pinned = -1;
         L.path.clear();
         const int64_t src_total = r.len;
         L.host_prefix = r.off >= src_total ? -1 : r.off;

@@ -75,9 +75,11 @@ struct PlannedConfig {
   int host_lane_classes = 0;       // lanes per direction to each other host (backend.h host_lanes; 0 = auto)
   std::map<NodeID, int64_t> link_rate;  // cap this rank's sends to a node (B/s; slow-link injection)
   int group_peers = 1;             // ops per peer and direction per group
-  int disk_readers = 4;            // NVMe reader threads (O_DIRECT pread into pinned bounce buffers)
+  // Reader threads: O_DIRECT preads of disk-tier chunks, and copies of chunks of
+  // pageable host layers, into the pinned bounce buffers.
+  int disk_readers = 4;
   bool disk_o_direct = true;       // false: buffered preads (tests of the fallback reporting)
-  int disk_ring = 8;               // pinned bounce buffers of chunk_bytes each
+  int disk_ring = 8;               // pinned bounce buffers of chunk_bytes each, allocated with the engine
   // One NVMe shared by every rank of the node: > 0 paces this rank's disk
   // reads through a node-wide budget of this many B/s (engine/node_pacer.h),
   // shared by every process that uses the same node_disk_key.
@@ -170,6 +172,7 @@ struct PlannedStats {
   // disk-tier bytes read with O_DIRECT (past every page cache of this OS) and
   // buffered (the filesystem refused O_DIRECT: they may come from memory)
   int64_t disk_direct_bytes = 0, disk_buffered_bytes = 0;
+  int64_t host_bounce_bytes = 0;  // bytes of pageable host layers copied through the bounce ring
   int64_t order_violations = 0;  // sends that waited on a recv with a larger key (must stay 0)
   int64_t scratch_landings = 0;  // recvs of chunks already staged / resident here (landed in scratch)
   int64_t scratch_buffers = 0;   // scratch-landing buffers allocated (the pool grows only when all are busy)
@@ -278,6 +281,7 @@ class PlannedEngine : public DataEngine {
     bool seeded = false;
     CrcManifest manifest;
     const uint8_t* host = nullptr;   // host-tier source (set at first staging)
+    int8_t host_pinned = -1;         // the copy queues can DMA from `host` (Backend::host_pinned; -1: not asked yet)
     std::string path;                // disk-tier source
     int64_t path_off = 0;
     bool src_packed = false;         // the source already holds the packed image (persisted layers)
@@ -313,10 +317,13 @@ class PlannedEngine : public DataEngine {
     Backend::CheckReq req{};
     double t0 = vclock::now();
   };
-  struct DiskRead {  // chunk of a disk-tier layer: pread into a bounce buffer, then H2D
+  // A chunk of a disk-tier layer (pread) or of a pageable host layer (memcpy
+  // from `host`) on its way into a bounce buffer, then H2D.
+  struct DiskRead {
     LayerID layer;
     int64_t chunk, file_off, len;
     std::string path;
+    const uint8_t* host = nullptr;
     uint8_t* bounce = nullptr;
     bool ok = true;
   };
@@ -392,8 +399,10 @@ class PlannedEngine : public DataEngine {
   bool has_local_source(Layer& L, LayerID id, int64_t c);  // staging can supply chunk c
   bool source_covers(Layer& L, LayerID id, int64_t c);      // chunk c is not a hole of a partial source
   void stage_chunk(Layer& L, LayerID id, int64_t c);
-  void stage_from(Layer& L, LayerID id, int64_t c, const uint8_t* src, uint8_t* bounce);
+  // `bounce_queue`: the H2D copy goes on the backend's bounce copy queue (chunks of pageable host layers).
+  void stage_from(Layer& L, LayerID id, int64_t c, const uint8_t* src, uint8_t* bounce, bool bounce_queue = false);
   void submit_disk(Layer& L, LayerID id, int64_t c);
+  bool alloc_ring();  // the bounce ring, once; false (and one warning) when the backend has no memory for it
   void pump_disk();
   void reader_loop();
   void landed(const Piece& p);
@@ -450,8 +459,9 @@ class PlannedEngine : public DataEngine {
   int64_t groups_issued_ = 0;
   std::atomic<bool> dead_{false};  // fault injection: this rank "crashed"
 
-  // disk tier: issue thread owns bounce_free_/disk_wait_; readers exchange via disk_mu_
+  // disk tier and pageable host layers: issue thread owns bounce_free_/disk_wait_; readers exchange via disk_mu_
   std::vector<uint8_t*> bounce_all_, bounce_free_;
+  bool ring_failed_ = false;  // alloc_ring found no pinned memory: pageable chunks stage directly
   // Scratch landings (a recv of a chunk this rank stages or holds): chunk-sized
   // device buffers, reused and freed only at shutdown - a free mid-session
   // (hipFree synchronizes the device) hung a rank-death recovery whose

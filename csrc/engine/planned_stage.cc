@@ -1,6 +1,7 @@
 // Planned engine (planned_engine.h), the local side of a chunk: staging from
 // host memory or the disk tier (O_DIRECT readers into pinned bounce buffers,
-// then H2D on the copy queues, fp8 packing on the way), tier pacing, and the
+// then H2D on the copy queues, fp8 packing on the way; pageable host memory
+// takes the same ring, copied in by the readers), tier pacing, and the
 // checks of staged and landed chunks - batched onto the verify queue
 // (flush_checks) - with their outcome: landed, partial coverage, NACK.
 #include "engine/planned_engine.h"
@@ -151,31 +152,54 @@ void PlannedEngine::stage_chunk(Layer& L, LayerID id, int64_t c) {
     }
   }
   if (L.host) {
-    stage_from(L, id, c, L.host + c * src_grid(L), nullptr);
+    // A copy from pageable memory would not return before the runtime has
+    // moved the bytes through staging of its own, one chunk at a time and with
+    // nothing enqueued behind it: such a chunk goes through the bounce ring
+    // instead. Without a ring it is copied directly.
+    if (L.host_pinned < 0) L.host_pinned = backend_->host_pinned(L.host) ? 1 : 0;
+    if (!L.host_pinned && alloc_ring()) submit_disk(L, id, c);
+    else stage_from(L, id, c, L.host + c * src_grid(L), nullptr);
   } else {
     submit_disk(L, id, c);
   }
 }
 
-void PlannedEngine::submit_disk(Layer& L, LayerID id, int64_t c) {
-  if (readers_.empty()) {
-    if (cfg_.node_disk_rate > 0 && !pacer_)
-      pacer_ = std::make_unique<NodePacer>(cfg_.node_disk_key.empty() ? "default" : cfg_.node_disk_key,
-                                           cfg_.node_disk_rate);
+bool PlannedEngine::alloc_ring() {
+  if (!bounce_all_.empty()) return true;
+  if (ring_failed_) return false;
+  try {
     for (int i = 0; i < std::max(1, cfg_.disk_ring); ++i) {
       uint8_t* b = backend_->alloc_host(cfg_.chunk_bytes);
       bounce_all_.push_back(b);
       bounce_free_.push_back(b);
     }
-    for (int i = 0; i < std::max(1, cfg_.disk_readers); ++i) readers_.push_back(vclock::spawn([this] { reader_loop(); }, "disk-reader"));
+  } catch (const std::exception& e) {
+    ring_failed_ = bounce_all_.empty();  // a shorter ring still works
+    log::warn(int64_t(self_node_)).i("buffers", int64_t(bounce_all_.size())).s("error", e.what())
+        .msg("no pinned memory for the whole bounce ring: without a buffer, pageable host chunks are copied directly");
   }
+  return !bounce_all_.empty();
+}
+
+void PlannedEngine::submit_disk(Layer& L, LayerID id, int64_t c) {
+  const bool from_host = L.host != nullptr;
+  if (!alloc_ring()) throw std::runtime_error("no pinned memory for the disk tier's bounce ring");
+  if (!from_host && cfg_.node_disk_rate > 0 && !pacer_)
+    pacer_ = std::make_unique<NodePacer>(cfg_.node_disk_key.empty() ? "default" : cfg_.node_disk_key,
+                                         cfg_.node_disk_rate);
+  if (readers_.empty())
+    for (int i = 0; i < std::max(1, cfg_.disk_readers); ++i) readers_.push_back(vclock::spawn([this] { reader_loop(); }, "disk-reader"));
   L.st[size_t(c)] = 3;
   DiskRead d;
   d.layer = id;
   d.chunk = c;
-  d.file_off = L.path_off + c * src_grid(L);
   d.len = src_len(L, c);
-  d.path = L.path;
+  if (from_host) {
+    d.host = L.host + c * src_grid(L);
+  } else {
+    d.file_off = L.path_off + c * src_grid(L);
+    d.path = L.path;
+  }
   disk_wait_.push_back(std::move(d));
   pump_disk();
 }
@@ -218,7 +242,7 @@ void PlannedEngine::pump_disk() {
       continue;
     }
     Layer& L = layers_[d.layer];
-    stage_from(L, d.layer, d.chunk, d.bounce, d.bounce);
+    stage_from(L, d.layer, d.chunk, d.bounce, d.bounce, d.host != nullptr);
   }
 }
 
@@ -234,6 +258,19 @@ void PlannedEngine::reader_loop() {
       if (disk_todo_.empty()) break;
       d = std::move(disk_todo_.front());
       disk_todo_.pop_front();
+    }
+    if (d.host) {  // a chunk of a pageable host layer: no file, no NVMe budget, no disk bytes
+      backend_->copy_host(d.bounce, d.host, d.len);
+      {
+        std::lock_guard<std::mutex> lk(stats_mu_);
+        stats_.host_bounce_bytes += d.len;
+      }
+      {
+        std::lock_guard<std::mutex> lk(disk_mu_);
+        disk_done_.push_back(std::move(d));
+      }
+      req_cv_.notify_all();
+      continue;
     }
     int& fd = fds[d.path];
     if (fd <= 0) {
@@ -295,14 +332,15 @@ void PlannedEngine::reader_loop() {
   ::free(aligned);
 }
 
-void PlannedEngine::stage_from(Layer& L, LayerID id, int64_t c, const uint8_t* src, uint8_t* bounce) {
+void PlannedEngine::stage_from(Layer& L, LayerID id, int64_t c, const uint8_t* src, uint8_t* bounce, bool bounce_queue) {
   const int64_t off = c * grid_;
   const int64_t len = std::min(grid_, L.size - off);
   const int64_t slen = src_len(L, c);
   trace::Scoped tr("dissem.stage");
   if (!L.dev) L.dev = backend_->alloc(L.size);
-  Ev e = cfg_.pack != 0 && !L.src_packed ? backend_->stage_pack(L.dev + off, src, slen, cfg_.pack_block, cfg_.pack)
-                                         : backend_->stage(L.dev + off, src, len);
+  Ev e = cfg_.pack != 0 && !L.src_packed
+             ? backend_->stage_pack(L.dev + off, src, slen, cfg_.pack_block, cfg_.pack, bounce_queue)
+             : backend_->stage(L.dev + off, src, len, bounce_queue);
   L.st[size_t(c)] = 1;
   L.rkey[size_t(c)] = Key{};
   set_chunk_ev(L, c, e);

@@ -10,10 +10,12 @@
 //
 // Timing model (SimTiming): a matched transfer occupies its directed link for
 // len / link_bps after the link's previous transfer (full duplex, links
-// independent); a staging copy occupies the rank's copy queue for
-// len / stage_bps. With copy_bytes = false no payload moves (timing-only runs
-// of full-size schedules in little memory). Multi-host fabrics (host, nic_bps)
-// also charge a cross-host transfer to both ends' NICs.
+// independent); a staging copy occupies the rank's PCIe - one timeline shared
+// by its copy queues - for len / stage_bps, and a reader's copy of a pageable
+// chunk into a bounce buffer that reader for len / host_copy_bps. With
+// copy_bytes = false no payload moves (timing-only runs of full-size schedules
+// in little memory). Multi-host fabrics (host, nic_bps) also charge a
+// cross-host transfer to both ends' NICs.
 //
 // Every time here is vclock::now(): with the virtual clock on (core/vclock.h)
 // the queues below wait in model time and a session's length is its modeled
@@ -204,6 +206,10 @@ struct Fabric {
 std::mutex g_fab_mu;
 std::map<std::string, std::shared_ptr<Fabric>> g_fabrics;
 
+// Host ranges a test declared pageable (sim_set_pageable): start -> length.
+std::mutex g_pageable_mu;
+std::map<const uint8_t*, int64_t> g_pageable;
+
 // A shrunk communicator runs over the same links and hosts, its ranks
 // renumbered without the dead ones: rank-indexed timing follows them.
 SimTiming survivors_timing(const SimTiming& t, const std::vector<int>& dead, int old_world) {
@@ -320,21 +326,42 @@ class SimBackend : public Backend {
     memset(p, 0, size_t(n));
   }
 
-  // Staging occupies the copy queue for n / stage_bps (timing model).
+  bool host_pinned(const uint8_t* p) override {
+    std::lock_guard<std::mutex> lk(g_pageable_mu);
+    auto it = g_pageable.upper_bound(p);
+    return it == g_pageable.begin() || p >= std::prev(it)->first + std::prev(it)->second;
+  }
+
+  // A reader's copy into a bounce buffer takes n / host_copy_bps of that reader's time.
+  void copy_host(uint8_t* dst, const uint8_t* src, int64_t n) override {
+    const double t0 = vclock::now();
+    if (fab_->timing.copy_bytes) memcpy(dst, src, size_t(n));
+    if (fab_->timing.host_copy_bps > 0) vclock::sleep_until(t0 + double(n) / fab_->timing.host_copy_bps);
+  }
+
+  // Staging occupies the rank's PCIe for n / stage_bps (timing model). The copy
+  // queues share that one link: a copy starts when the link is free of the
+  // copies before it, so together they never exceed stage_bps.
   void stage_delay(double t0, int64_t n) {
     const double bps = fab_->timing.stage_bps;
     if (bps <= 0) return;
+    double end;
+    {
+      std::lock_guard<std::mutex> lk(pcie_mu_);
+      t0 = std::max(t0, pcie_free_);
+      end = pcie_free_ = t0 + double(n) / bps;
+    }
     if (fab_->timing.trace) {
       std::lock_guard<std::mutex> lk(fab_->mu);
-      fab_->stats.stages.emplace_back(rank_, t0, t0 + double(n) / bps, n);
+      fab_->stats.stages.emplace_back(rank_, t0, end, n);
     }
-    vclock::sleep_until(t0 + double(n) / bps);
+    vclock::sleep_until(end);
   }
 
-  Ev stage(uint8_t* dst, const uint8_t* src, int64_t n) override {
+  Ev stage(uint8_t* dst, const uint8_t* src, int64_t n, bool bounce) override {
     auto [id, ev] = make_event();
     const bool copy = fab_->timing.copy_bytes;
-    copy_.push([=] {
+    (bounce ? bounce_ : copy_).push([=] {
       const double t0 = vclock::now();
       if (copy) memcpy(dst, src, size_t(n));
       stage_delay(t0, n);
@@ -343,10 +370,10 @@ class SimBackend : public Backend {
     return id;
   }
 
-  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block, int format) override {
+  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block, int format, bool bounce) override {
     auto [id, ev] = make_event();
     const bool copy = fab_->timing.copy_bytes;
-    copy_.push([=] {
+    (bounce ? bounce_ : copy_).push([=] {
       const double t0 = vclock::now();
       const int64_t n = n_src / 2;
       if (copy && format == kPackMxfp4) mxfp4::pack_host(reinterpret_cast<const uint16_t*>(src), n, dst, dst + n / 2);
@@ -566,11 +593,13 @@ class SimBackend : public Backend {
   void sync_all() override {
     for (auto& q : comm_) q->drain();
     copy_.drain();
+    bounce_.drain();
     verify_.drain();
   }
   void destroy(bool) override {
     for (auto& q : comm_) q->stop();
     copy_.stop();
+    bounce_.stop();
     verify_.stop();
   }
 
@@ -604,6 +633,9 @@ class SimBackend : public Backend {
   std::string error_;
   std::vector<std::unique_ptr<Queue>> comm_;
   Queue copy_, verify_;
+  Queue bounce_;  // copy queue of the bounce buffers filled from pageable host memory
+  std::mutex pcie_mu_;
+  double pcie_free_ = 0;  // timing model: this rank's PCIe is busy until then (vclock::now() s)
 };
 
 }  // namespace
@@ -617,6 +649,12 @@ void sim_set_timing(const std::string& comm_key, const SimTiming& t) {
   std::lock_guard<std::mutex> lk(f->mu);
   f->timing = t;
   f->link_free.clear();
+}
+
+void sim_set_pageable(const uint8_t* p, int64_t n, bool on) {
+  std::lock_guard<std::mutex> lk(g_pageable_mu);
+  if (on) g_pageable[p] = n;
+  else g_pageable.erase(p);
 }
 
 void sim_clear_trace(const std::string& comm_key) {

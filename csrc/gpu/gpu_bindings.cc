@@ -212,6 +212,10 @@ void register_gpu_bindings(PyObject* module) {
         return alloc_pinned(n);
       })
       .def_static("malloc", [](int64_t n) { return HostBuffer::alloc(n, true); })
+      .def_static("pinned_live_bytes", &pinned_live_bytes,
+                  "pinned bytes HostBuffer.pinned has handed out and not yet freed (what DISSEM_PINNED_LIMIT_BYTES caps)")
+      .def_property_readonly("is_pinned", [](const HostBuffer& b) { return host_pointer_pinned(b.ptr); },
+                             "the GPU's copy queues can DMA from this buffer (pinned or registered memory)")
       // Node-shared host memory (POSIX shm): one process creates `name`, the
       // others of the node map it; `pin` registers the mapping with HIP in this
       // process (page-locked, DMA-able by this rank's GPU over its own PCIe).
@@ -245,7 +249,9 @@ void register_gpu_bindings(PyObject* module) {
         if (pin) {
           hipError_t e = hipHostRegister(p, size_t(n), hipHostRegisterDefault);
           if (e != hipSuccess) {
+            (void)hipGetLastError();  // or the next kernel launch would report it
             munmap(p, size_t(n));
+            if (create) shm_unlink(nm.c_str());
             throw std::runtime_error("hipHostRegister " + nm + ": " + hipGetErrorString(e));
           }
         }

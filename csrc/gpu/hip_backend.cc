@@ -5,6 +5,7 @@
 
 #include <chrono>
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -54,7 +55,7 @@ class HipBackend : public Backend {
       comm_.push_back(s);
     }
     nccl_.assign(size_t(lanes), nullptr);
-    const int keep_free = part > 0 ? part : cfg_.reserve_cus;  // CUs the copy streams stay off
+    const int keep_free = copy_keep_free_ = part > 0 ? part : cfg_.reserve_cus;  // CUs the copy streams stay off
     copy_ = create_stream_reserving(cfg_.device, keep_free);
     // Two SDMA copy queues in alternation keep the PCIe link busier across copy
     // boundaries (h2dbench: 56.8 -> 57.4 GB/s; bench 56.0 -> 56.9 GB/s). With
@@ -231,9 +232,12 @@ class HipBackend : public Backend {
   }
   uint8_t* alloc_host(int64_t n) override {
     void* p = nullptr;
-    HIP_OK(hipHostMalloc(&p, size_t(std::max<int64_t>(n, 4096)), hipHostMallocDefault));
+    const hipError_t e = hipHostMalloc(&p, size_t(std::max<int64_t>(n, 4096)), hipHostMallocDefault);
+    if (e != hipSuccess) (void)hipGetLastError();  // or the next kernel launch would report it
+    HIP_OK(e);
     return static_cast<uint8_t*>(p);
   }
+  bool host_pinned(const uint8_t* p) override { return host_pointer_pinned(p); }
   void free_host(uint8_t* p) override { (void)hipHostFree(p); }
   void zero_sync(uint8_t* p, int64_t n) override {
     // On the copy queue, never a comm lane: a lane may still hold an RCCL
@@ -242,19 +246,31 @@ class HipBackend : public Backend {
     HIP_OK(hipStreamSynchronize(copy_));
   }
 
-  Ev stage(uint8_t* dst, const uint8_t* src, int64_t n) override {
-    hipStream_t s = copy2_ && (flip_ ^= true) ? copy2_ : copy_;
+  // The copy queue of a staging call: the two pinned-source queues in
+  // alternation, or - for a bounce buffer filled from pageable memory - a third
+  // with a hardware queue of its own, created when the first such copy comes.
+  // On the other two that copy would land behind every pinned copy already
+  // queued (about a thousand at N = 1) and hold its ring buffer until then.
+  int copy_queue(bool bounce) {
+    if (!bounce) return copy2_ && (flip_ ^= true) ? 1 : 0;
+    if (!bounce_) bounce_ = create_stream_reserving(cfg_.device, copy_keep_free_, /*dedicated=*/true);
+    return 2;
+  }
+  hipStream_t copy_stream(int q) const { return q == 2 ? bounce_ : q == 1 ? copy2_ : copy_; }
+
+  Ev stage(uint8_t* dst, const uint8_t* src, int64_t n, bool bounce) override {
+    hipStream_t s = copy_stream(copy_queue(bounce));
     HIP_OK(hipMemcpyAsync(dst, src, size_t(n), hipMemcpyHostToDevice, s));
     return record(s);
   }
 
-  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block, int format) override {
+  Ev stage_pack(uint8_t* dst, const uint8_t* src, int64_t n_src, int block, int format, bool bounce) override {
     // bf16 lands in a device scratch chunk, then the gfx950 pack kernel writes
     // the packed chunk into the layer slot. One scratch per copy queue: both
     // steps are ordered on that queue, and packing (~22 us per 64 MiB) is
     // noise next to the PCIe copy (~1.2 ms).
-    const int q = copy2_ && (flip_ ^= true) ? 1 : 0;
-    hipStream_t s = q ? copy2_ : copy_;
+    const int q = copy_queue(bounce);
+    hipStream_t s = copy_stream(q);
     if (n_src > scratch_bytes_[q]) {
       // Sized for a whole source chunk on first use, so it never grows in a
       // session: hipFree synchronizes the device, comm lanes included.
@@ -421,7 +437,7 @@ class HipBackend : public Backend {
     }
     // Bounded drain of every queue (an aborted kernel must have exited).
     std::vector<hipStream_t> all(comm_);
-    for (hipStream_t s : {copy_, verify_, copy2_}) all.push_back(s);
+    for (hipStream_t s : {copy_, verify_, copy2_, bounce_}) all.push_back(s);
     for (hipStream_t s : all) {
       if (!s) continue;
       hipEvent_t e;
@@ -464,6 +480,7 @@ class HipBackend : public Backend {
     for (hipStream_t s : comm_) (void)hipStreamSynchronize(s);
     (void)hipStreamSynchronize(copy_);
     if (copy2_) (void)hipStreamSynchronize(copy2_);
+    if (bounce_) (void)hipStreamSynchronize(bounce_);
     (void)hipStreamSynchronize(verify_);
   }
   void destroy(bool abort) override {
@@ -496,6 +513,7 @@ class HipBackend : public Backend {
     for (hipStream_t s : comm_) (void)hipStreamDestroy(s);
     (void)hipStreamDestroy(copy_);
     if (copy2_) (void)hipStreamDestroy(copy2_);
+    if (bounce_) (void)hipStreamDestroy(bounce_);
     (void)hipStreamDestroy(verify_);
   }
 
@@ -534,6 +552,8 @@ class HipBackend : public Backend {
   std::vector<hipStream_t> comm_;  // one per lane
   hipStream_t copy_ = nullptr, verify_ = nullptr;
   hipStream_t copy2_ = nullptr;  // second H2D queue
+  hipStream_t bounce_ = nullptr;  // H2D queue of bounce buffers filled from pageable memory (copy_queue)
+  int copy_keep_free_ = 0;        // CUs the copy streams stay off
   std::map<uint8_t*, std::pair<int64_t, std::vector<void*>>> regs_;  // registered slots: size, handle per lane
   bool flip_ = false;
   std::vector<ncclComm_t> nccl_;  // one per lane (lane 0: the world communicator, others split from it)
@@ -544,8 +564,8 @@ class HipBackend : public Backend {
   std::vector<hipEvent_t> timed_pool_;
   void* ws_ = nullptr;  // fold words of the verify launches
   int verify_cus_ = 0;  // CUs of the verify stream (0 = all): kernels.h `cus`
-  void* scratch_[2] = {nullptr, nullptr};  // bf16 landing chunk for stage_pack, per copy queue
-  int64_t scratch_bytes_[2] = {0, 0};
+  void* scratch_[3] = {nullptr, nullptr, nullptr};  // bf16 landing chunk for stage_pack, per copy queue
+  int64_t scratch_bytes_[3] = {0, 0, 0};
   uint32_t* crc_host_ = nullptr;
   uint32_t* crc_dev_ = nullptr;
   std::vector<hipEvent_t> pool_;  // issue-thread only
@@ -586,22 +606,48 @@ hipStream_t create_stream_on_last(int device, int n) {
   return s;
 }
 
+bool host_pointer_pinned(const void* p) {
+  // Plain memory: an error from older runtimes, "unregistered" from newer ones.
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return a.type != hipMemoryTypeUnregistered;
+}
+
+namespace {
+std::atomic<int64_t> g_pinned_live{0};  // pinned bytes alloc_pinned has handed out and not yet freed
+}
+
+int64_t pinned_live_bytes() { return g_pinned_live.load(); }
+
 std::shared_ptr<HostBuffer> alloc_pinned(int64_t size) {
   void* p = nullptr;
   const size_t n = size_t(std::max<int64_t>(size, 1));
-  const hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
+  // DISSEM_PINNED_LIMIT_BYTES caps the live pinned bytes handed out here: what
+  // a small pinned pool does to a large model, at any size and on any machine.
+  const char* cap = getenv("DISSEM_PINNED_LIMIT_BYTES");
+  const bool capped = cap && *cap && g_pinned_live.load() + int64_t(n) > atoll(cap);
+  const hipError_t e = capped ? hipErrorOutOfMemory : hipHostMalloc(&p, n, hipHostMallocDefault);
   if (e == hipErrorOutOfMemory) {
     // The pinned pool is smaller than host memory on some machines (64 GiB of
-    // 300 on a virtual one): the layers past it live in pageable memory, which
-    // the runtime stages through pinned buffers of its own - slower, and said so.
-    (void)hipGetLastError();
+    // 300 on a virtual one): the layers past it live in pageable memory. The
+    // engine finds that out per layer (Backend::host_pinned) and moves their
+    // chunks through its pinned bounce ring, copied in by its reader threads.
+    if (!capped) (void)hipGetLastError();
     if (posix_memalign(&p, 4096, n) != 0) throw std::bad_alloc();
-    log::warn(0).i("bytes", int64_t(n)).msg("pinned host memory exhausted: buffer is pageable, its copies are staged");
+    log::warn(0).i("bytes", int64_t(n))
+        .msg(capped ? "pinned host memory capped (DISSEM_PINNED_LIMIT_BYTES): buffer is pageable, staged through the bounce ring"
+                    : "pinned host memory exhausted: buffer is pageable, staged through the bounce ring");
     return HostBuffer::wrap(static_cast<uint8_t*>(p), size, std::shared_ptr<void>(p, ::free));
   }
   HIP_OK(e);
-  return HostBuffer::wrap(static_cast<uint8_t*>(p), size,
-                          std::shared_ptr<void>(p, [](void* q) { (void)hipHostFree(q); }));
+  g_pinned_live += int64_t(n);
+  return HostBuffer::wrap(static_cast<uint8_t*>(p), size, std::shared_ptr<void>(p, [n](void* q) {
+                            (void)hipHostFree(q);
+                            g_pinned_live -= int64_t(n);
+                          }));
 }
 
 std::string nccl_unique_id(int count) {

@@ -1,7 +1,8 @@
 // MI355X backend of the planned engine: HBM slots (hipMalloc), RCCL grouped
 // point-to-point over xGMI on one communicator + stream per comm lane,
-// hipMemcpyAsync staging from pinned host memory (one or two copy streams), and
-// the gfx950 CRC32C kernel (verify stream).
+// hipMemcpyAsync staging from pinned host memory (one or two copy streams, and
+// a third, created on first use, for bounce buffers filled from pageable
+// memory), and the gfx950 CRC32C kernel (verify stream).
 //
 // Hardware queues: HIP maps ordinary streams onto a pool of GPU_MAX_HW_QUEUES
 // (4) queues, so streams can share one; a CU-masked stream always gets a queue
@@ -61,7 +62,13 @@ hipStream_t create_stream_reserving(int device, int reserve, bool dedicated = fa
 hipStream_t create_stream_on_last(int device, int cus);
 
 std::unique_ptr<Backend> make_hip_backend(const HipBackendConfig& cfg);
+// Pinned host memory, or - when the pool is exhausted, or the request would
+// take the live pinned bytes handed out here (pinned_live_bytes) past
+// DISSEM_PINNED_LIMIT_BYTES - page-aligned pageable memory, with a warning.
 std::shared_ptr<HostBuffer> alloc_pinned(int64_t size);
+int64_t pinned_live_bytes();
+// Is `p` pinned or registered host memory (hipPointerGetAttributes), so that a copy queue can DMA from it?
+bool host_pointer_pinned(const void* p);
 std::string nccl_unique_id(int count = 1);  // `count` ncclUniqueIds, concatenated
 
 }  // namespace dissem
