@@ -5,6 +5,7 @@
 #   make sanitize   -> build/tests/*_{tsan,asan} (host-only core under Thread/Address sanitizer)
 #   make sanitize-mxfp6 -> build/tests/mxfp6_selftest_asan (the MXFP6 host codec under ASan + UBSan), and runs it
 #   make sanitize-attn  -> build/tests/attn_decode_selftest_asan (the attention's launch sizing under ASan + UBSan), and runs it
+#   make sanitize-attn-prefill -> build/tests/attn_prefill_selftest_asan (the prefill attention's launch sizing, the same way), and runs it
 #
 # The extension links the HIP runtime and RCCL that PyTorch-ROCm ships, so one
 # process never holds two HIP runtimes (torch is imported before _core).
@@ -121,7 +122,17 @@ $(BUILD)/tests/attn_decode_selftest_asan: csrc/tests/attn_decode_selftest.cc csr
 sanitize-attn: $(BUILD)/tests/attn_decode_selftest_asan
 	$(BUILD)/tests/attn_decode_selftest_asan
 
+# The same for the prefill attention and the many-token rope (kernels/attn_prefill_plan.h):
+# the grids walked with the kernels' own index arithmetic over exact-size buffers.
+$(BUILD)/tests/attn_prefill_selftest_asan: csrc/tests/attn_prefill_selftest.cc csrc/kernels/attn_prefill_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	  -static-libasan -static-libubsan -o $@ csrc/tests/attn_prefill_selftest.cc
+
+sanitize-attn-prefill: $(BUILD)/tests/attn_prefill_selftest_asan
+	$(BUILD)/tests/attn_prefill_selftest_asan
+
 clean:
 	rm -rf $(BUILD) $(PKG)/_core*.so bin/diskspeed bin/h2dbench bin/contention
 
-.PHONY: all tools sanitize sanitize-mxfp6 sanitize-attn clean
+.PHONY: all tools sanitize sanitize-mxfp6 sanitize-attn sanitize-attn-prefill clean

@@ -8,6 +8,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <array>
 #include <cerrno>
 #include <chrono>
 #include <cstring>
@@ -23,6 +24,7 @@
 #include "gpu/gpu_api.h"
 #include "gpu/hip_backend.h"
 #include "kernels/attn_decode_plan.h"
+#include "kernels/attn_prefill_plan.h"
 #include "kernels/kernels.h"
 
 namespace py = pybind11;
@@ -769,6 +771,40 @@ void register_gpu_bindings(PyObject* module) {
         py::arg("kv_heads"), py::arg("d"), py::arg("capacity"), py::arg("max_len"));
   // positions of one workgroup's chunk: chunk boundaries are multiples of it for every batch
   m.def("attn_decode_chunk", []() { return kern::kAttnDecodeChunk; });
+  // causal attention of S tokens a sequence against K / V in HBM, and their rope and append
+  // (kernels/attn_prefill.hip); stream-ordered. A shape or stride outside the contract is a ValueError
+  // before any launch. kstride, vstride: (batch, head, position) element strides.
+  m.def("attn_prefill", [](uint64_t q, uint64_t k, uint64_t v, uint64_t start, int64_t b, int64_t s, int64_t heads,
+                           int64_t kv_heads, int64_t d, int64_t t, std::array<int64_t, 3> kstride,
+                           std::array<int64_t, 3> vstride, uint64_t y, bool y_bf16, uint64_t stream) {
+    if (!kern::attn_prefill_plan(b, s, heads, kv_heads, d, t, kstride.data(), vstride.data()).ok)
+      throw std::invalid_argument("attn_prefill: a shape or stride the kernel does not serve");
+    check(kern::attn_prefill(reinterpret_cast<const uint16_t*>(q), reinterpret_cast<const uint16_t*>(k),
+                             reinterpret_cast<const uint16_t*>(v), reinterpret_cast<const int32_t*>(start), b, s, heads,
+                             kv_heads, d, t, kstride.data(), vstride.data(), reinterpret_cast<void*>(y), y_bf16,
+                             as_stream(stream)),
+          "attn_prefill");
+  }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("start"), py::arg("b"), py::arg("s"), py::arg("heads"),
+     py::arg("kv_heads"), py::arg("d"), py::arg("t"), py::arg("kstride"), py::arg("vstride"), py::arg("y"),
+     py::arg("y_bf16"), py::arg("stream") = 0);
+  m.def("attn_rope_append_seq", [](uint64_t q, int64_t ldq, uint64_t k, int64_t ldk, uint64_t v, int64_t ldv,
+                                   uint64_t start, uint64_t cos, uint64_t sin, int64_t b, int64_t s, int64_t heads,
+                                   int64_t kv_heads, int64_t d, int64_t capacity, uint64_t q_out, uint64_t k_cache,
+                                   uint64_t v_cache, uint64_t stream) {
+    if (!kern::attn_rope_seq_plan(b, s, heads, kv_heads, d, capacity, ldq, ldk, ldv).ok)
+      throw std::invalid_argument("attn_rope_append_seq: a shape or stride the kernel does not serve");
+    check(kern::attn_rope_append_seq(reinterpret_cast<const uint16_t*>(q), ldq, reinterpret_cast<const uint16_t*>(k),
+                                     ldk, reinterpret_cast<const uint16_t*>(v), ldv,
+                                     reinterpret_cast<const int32_t*>(start), reinterpret_cast<const float*>(cos),
+                                     reinterpret_cast<const float*>(sin), b, s, heads, kv_heads, d, capacity,
+                                     reinterpret_cast<uint16_t*>(q_out), reinterpret_cast<uint16_t*>(k_cache),
+                                     reinterpret_cast<uint16_t*>(v_cache), as_stream(stream)),
+          "attn_rope_append_seq");
+  }, py::arg("q"), py::arg("ldq"), py::arg("k"), py::arg("ldk"), py::arg("v"), py::arg("ldv"), py::arg("start"),
+     py::arg("cos"), py::arg("sin"), py::arg("b"), py::arg("s"), py::arg("heads"), py::arg("kv_heads"), py::arg("d"),
+     py::arg("capacity"), py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("stream") = 0);
+  // (BQ, BK): query rows of a workgroup, positions of a K / V tile
+  m.def("attn_prefill_tiles", []() { return std::make_pair(kern::kAttnPrefillBQ, kern::kAttnPrefillBK); });
 
   // ---- RCCL path on one GPU: a one-rank communicator driven through the same
   // Backend::group / crc calls the planned engine issues. `rounds` groups of

@@ -345,5 +345,59 @@ hipError_t attn_decode(const uint16_t* q, const uint16_t* k_cache, const uint16_
                        int64_t B, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, int64_t max_len,
                        void* ws, int64_t ws_bytes, void* y, bool y_bf16, hipStream_t s);
 
+// ---- attn_prefill.hip: causal attention of S new tokens per sequence against K
+// and V in HBM (prefill, chunked prefill, multi-token extend), and their rope
+// and cache append.
+//
+// attn_prefill, ONE launch: for sequence b, query row i in [0, S) and head h,
+// y[b, i, h * d ...] = softmax(q[b, i, h] . K[b, h / group, :n] / sqrt(d)) V[b, h
+// / group, :n] with n = start[b] + i + 1. q is bf16 [B, S, heads, d], contiguous;
+// K and V are bf16 [B, kv_heads, T, d] with unit stride along d and explicit
+// int64 element strides {batch, head, position} (kstride, vstride), each a
+// multiple of 8 and not negative, on 16-byte-aligned bases: a KVCache (T its
+// capacity) and the k / v column slices of one merged q/k/v projection (position
+// stride (heads + 2 kv_heads) * d) are both read where they lie. start is int32
+// [B] on the device, or null for all zero; it is never read on the host. A
+// negative start[b] counts as 0. A row whose position start[b] + i is >= T gives
+// a zero row and loads nothing. Positions at or behind min(start[b] + S, T) are
+// never read: the cache there may hold NaN. d is 32, 64 or 128, any group >= 1,
+// S and T at most 2^20, B at most 2^20, B * heads * ceil(S / kAttnPrefillBQ) a
+// 31-bit grid. y is [B, S, heads * d] f32 or bf16, the bf16 result the f32
+// result rounded to nearest even. Stream-ordered; no workspace, no atomics, no
+// allocation, no synchronization. Anything else: hipErrorInvalidValue.
+// A workgroup of four waves serves one (b, h, tile of kAttnPrefillBQ = 128 rows),
+// each wave 32 rows as two MFMA column blocks; K and V tiles of kAttnPrefillBK =
+// 64 positions at absolute positions 0, BK, ... are fetched once per workgroup
+// into double-buffered, XOR-swizzled LDS; S^T = K Q^T and O^T = V^T P^T on
+// v_mfma_f32_16x16x32_bf16 with f32 scores, online softmax per 32-position step
+// and P rounded to bf16 (attn_decode's numerics). A row's bits are a function of
+// its q row, its position and the K / V rows before and at it - the same for any
+// B, S, start, slot, T, strides and query tile.
+// Inside a sequence's valid positions: a NaN in a K row makes the rows that see
+// that position NaN in the query heads of its KV head; a non-finite V element at
+// position j makes that d non-finite in the rows at j and behind it - and in the
+// rows BEFORE j whose wave still visits j's 32-position step (rows fewer than
+// 63 positions before j): there it meets a weight of exactly 0, and 0 * inf is NaN. Other rows, heads and
+// sequences keep their bits.
+//
+// attn_rope_append_seq, ONE launch: attn_rope_append for S tokens a sequence.
+// q, k, v are bf16 rows n = b * S + i with unit stride and row strides ldq, ldk,
+// ldv (multiples of 8, 16-byte-aligned bases: the slices of one merged
+// projection or three buffers); token i of sequence b has position start[b] + i
+// (start int32 [B] on the device, or null for zero). q_out[b, i, h] = rope(q) at
+// that position (bf16 [B, S, heads, d], contiguous), k_cache[b, h, position] =
+// rope(k), v_cache[b, h, position] = v, the caches [B, kv_heads, capacity, d]
+// contiguous, cos and sin f32 [capacity, d]. The arithmetic is attn_rope_append's
+// (two rounded products, one rounded sum, no FMA). A position outside [0,
+// capacity) writes nothing to the caches and a zero q_out row. 16-byte loads and
+// stores: a thread rotates 8 d of the lower half and their partners of the upper.
+hipError_t attn_prefill(const uint16_t* q, const uint16_t* k, const uint16_t* v, const int32_t* start, int64_t B,
+                        int64_t S, int64_t heads, int64_t kv_heads, int64_t d, int64_t T, const int64_t* kstride,
+                        const int64_t* vstride, void* y, bool y_bf16, hipStream_t s);
+hipError_t attn_rope_append_seq(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
+                                int64_t ldv, const int32_t* start, const float* cos, const float* sin, int64_t B,
+                                int64_t S, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity,
+                                uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

@@ -383,7 +383,7 @@ class KVCache:
 
 def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool = True,
                     fuse_gated: bool = False, tiled: bool = False, act: Optional[str] = None,
-                    cache: Optional[KVCache] = None) -> torch.Tensor:
+                    cache: Optional[KVCache] = None, attn: Optional[str] = None, extend: bool = False) -> torch.Tensor:
     """One decoder layer on x [batch, seq, hidden] (causal self-attention; with `cache`
     the prefill of a KV cache, see the end).
     Each parameter is a bf16 tensor or a PackedParam: a packed linear runs from its
@@ -411,17 +411,58 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     `cache` (opt-in): the pass is the prefill of that `KVCache` - the rotated k and the
     v of all seq positions are also stored at positions [0, seq) of every sequence,
     `cache.lens` becomes seq everywhere and `cache.max_len` seq; `decoder_step` goes on
-    from there. The result is the same with and without it."""
+    from there. The result is the same with and without it.
+    `attn="mfma"` (opt-in) runs the attention stage on the gfx950 kernels (on the CPU,
+    their host routes): q, k and v go from `_qkv`, where they lie, through
+    ``ops.rope_append_seq`` into the cache, and ``ops.attn_prefill`` reads K and V from
+    the cache once per query tile - no `_rope` passes, no slice-assign and no
+    repeat_interleave of K and V. Without a `cache`, a transient [batch, kv_heads, seq,
+    head_dim] pair with its rotary tables is allocated for the call. Any other `attn`
+    raises ValueError.
+    `extend=True` (needs `cache` and `attn="mfma"`): the seq tokens of sequence b go to
+    positions [lens[b], lens[b] + seq) of a cache that already holds lens[b] tokens and
+    attend to all of them - chunked prefill and multi-token extend. `cache.lens` advances
+    by seq on the device and `cache.max_len` by seq; ValueError when max_len + seq exceeds
+    the capacity. Without `extend` a pass with a cache writes positions [0, seq) and sets
+    lens = seq, as above."""
     if act not in (None, "mxfp8"):
         raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
+    if attn not in (None, "mfma"):
+        raise ValueError(f"attn must be None or 'mfma', got {attn!r}")
+    if extend and (cache is None or attn != "mfma"):
+        raise ValueError("extend=True needs a cache and attn='mfma'")
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     if cache is not None:
         _check_cache(cache, spec, b, x.device)
         if s > cache.capacity:
             raise ValueError(f"{s} positions do not fit a cache of {cache.capacity}")
+        if extend and cache.max_len + s > cache.capacity:
+            raise ValueError(f"{cache.max_len} + {s} positions do not fit a cache of {cache.capacity}")
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
     q, k, v = _qkv(h, p, fuse, tiled, act)
+    if attn == "mfma":
+        from ..ops import attn_prefill, rope_append_seq
+
+        if cache is None:
+            kc = torch.empty(b, nkv, s, hd, dtype=torch.bfloat16, device=x.device)
+            vc = torch.empty_like(kc)
+            cos, sin = _rope_tables(s, hd, spec.rope_theta, x.device)
+        else:
+            kc, vc, cos, sin = cache.k, cache.v, cache.cos, cache.sin
+        start = cache.lens if extend else None
+        q = rope_append_seq(q, k, v, cos, sin, kc, vc, start)
+        a = attn_prefill(q, kc, vc, start, out_dtype=x.dtype)
+        if extend:
+            cache.lens.add_(s)
+            cache.max_len += s
+        elif cache is not None:
+            cache.lens.fill_(s)
+            cache.max_len = s
+        x = x + _linear(a, p["o_proj"], tiled, act)
+        h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
+        return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled, act), p["down_proj"],
+                           tiled, act)
     q = q.view(b, s, nh, hd).transpose(1, 2)
     k = k.view(b, s, nkv, hd).transpose(1, 2)
     v = v.view(b, s, nkv, hd).transpose(1, 2)
