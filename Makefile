@@ -111,10 +111,10 @@ $(BUILD)/tests/mxfp6_selftest_asan: csrc/tests/mxfp6_selftest.cc csrc/core/mxfp6
 sanitize-mxfp6: $(BUILD)/tests/mxfp6_selftest_asan
 	$(BUILD)/tests/mxfp6_selftest_asan
 
-# The host-side sizing of the single-token attention (kernels/attn_decode_plan.h)
+# The host-side sizing of the single-token attention (kernels/attn_plan.h)
 # with its own main: an exact-size workspace walked with the kernels' own index
 # arithmetic, and the contract's extremes, under ASan + UBSan.
-$(BUILD)/tests/attn_decode_selftest_asan: csrc/tests/attn_decode_selftest.cc csrc/kernels/attn_decode_plan.h
+$(BUILD)/tests/attn_decode_selftest_asan: csrc/tests/attn_decode_selftest.cc csrc/kernels/attn_plan.h
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
 	  -static-libasan -static-libubsan -o $@ csrc/tests/attn_decode_selftest.cc
@@ -122,9 +122,9 @@ $(BUILD)/tests/attn_decode_selftest_asan: csrc/tests/attn_decode_selftest.cc csr
 sanitize-attn: $(BUILD)/tests/attn_decode_selftest_asan
 	$(BUILD)/tests/attn_decode_selftest_asan
 
-# The same for the prefill attention and the many-token rope (kernels/attn_prefill_plan.h):
+# The same for the prefill attention and the many-token rope (kernels/attn_plan.h):
 # the grids walked with the kernels' own index arithmetic over exact-size buffers.
-$(BUILD)/tests/attn_prefill_selftest_asan: csrc/tests/attn_prefill_selftest.cc csrc/kernels/attn_prefill_plan.h
+$(BUILD)/tests/attn_prefill_selftest_asan: csrc/tests/attn_prefill_selftest.cc csrc/kernels/attn_plan.h
 	@mkdir -p $(dir $@)
 	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
 	  -static-libasan -static-libubsan -o $@ csrc/tests/attn_prefill_selftest.cc

@@ -23,8 +23,7 @@
 #include "core/mxfp6.h"
 #include "gpu/gpu_api.h"
 #include "gpu/hip_backend.h"
-#include "kernels/attn_decode_plan.h"
-#include "kernels/attn_prefill_plan.h"
+#include "kernels/attn_plan.h"
 #include "kernels/kernels.h"
 
 namespace py = pybind11;

@@ -7,21 +7,10 @@
 // (sequence, KV head, chunk of kAttnDecodeChunk positions) and all the query
 // heads of that KV head, padded to the 16 of an MFMA tile, so a K and a V row
 // are fetched once per KV head. K and V go from global memory straight to the
-// MFMA operands, 16 B a lane, with no LDS in between:
-//
-//   S^T = K Q^T on v_mfma_f32_16x16x32_bf16, K the A operand (a lane loads 8
-//   consecutive d of one position), Q^T the B operand, loaded once. A lane then
-//   holds, for ONE head (lane & 15), the scores of 8 of the step's 32 positions,
-//   so the online softmax needs two xor shuffles for the maximum and nothing
-//   else across lanes.
-//
-//   O^T = V^T P^T: those 8 bf16-rounded P are, as they lie, the lane's B operand
-//   (the MFMA's sum over k does not care which position sits in which k slot, as
-//   long as A agrees). For A a lane loads D / 16 consecutive d of its 8
-//   positions and transposes them in registers - one 16-bit pack per operand
-//   word - which gives row (lane & 15) of D / 16 tiles of V^T: tile t holds
-//   d = row * (D / 16) + t. The accumulator's column is the head again, so the
-//   softmax's rescale factor applies per lane.
+// MFMA operands, 16 B a lane, with no LDS in between, in the lane map of
+// attn_mma.h: S^T = K Q^T with Q^T loaded once, its column the query head; the
+// online softmax per 32-position step; O^T = V^T P^T with V^T transposed in
+// registers from D / 16 consecutive d of the lane's 8 positions.
 //
 // Wave w takes the 32-position steps w and w + 4 of the chunk; the four waves'
 // (m, l, o) meet in LDS and are merged in wave order into the chunk's partial
@@ -32,9 +21,9 @@
 // max_len or the capacity except which workgroups exist.
 #include <hip/hip_runtime.h>
 
-#include "kernels/attn_decode_plan.h"
+#include "kernels/attn_mma.h"
+#include "kernels/attn_plan.h"
 #include "kernels/kernels.h"
-#include "kernels/mxfp4_mma.h"
 
 namespace dissem {
 namespace kern {
@@ -46,8 +35,6 @@ constexpr int kWaves = 4;
 constexpr int kStep = 32;                         // positions of one wave step
 constexpr int kStepsPerWave = kC / (kStep * kWaves);
 static_assert(kC == kStep * kWaves * kStepsPerWave, "a chunk is a whole number of steps per wave");
-
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(uint32_t(h) << 16); }
 
 // ---------------------------------------------------------------- rope_append
 template <int D>
@@ -85,30 +72,6 @@ __global__ void __launch_bounds__(D) rope_append_kernel(const uint16_t* __restri
 }
 
 // ---------------------------------------------------------------- attn_decode
-template <int N>
-struct Words;
-template <>
-struct Words<4> {
-  uint32_t w[4];
-  __device__ __forceinline__ void load(const uint16_t* p) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    w[0] = u.x, w[1] = u.y, w[2] = u.z, w[3] = u.w;
-  }
-};
-template <>
-struct Words<2> {
-  uint32_t w[2];
-  __device__ __forceinline__ void load(const uint16_t* p) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    w[0] = u.x, w[1] = u.y;
-  }
-};
-template <>
-struct Words<1> {
-  uint32_t w[1];
-  __device__ __forceinline__ void load(const uint16_t* p) { w[0] = *reinterpret_cast<const uint32_t*>(p); }
-};
-
 template <int D>
 __global__ void __launch_bounds__(64 * kWaves) attn_partial_kernel(const uint16_t* __restrict__ q,
                                                                    const uint16_t* __restrict__ k_cache,
@@ -146,7 +109,7 @@ __global__ void __launch_bounds__(64 * kWaves) attn_partial_kernel(const uint16_
     qf[ks] = as_frag(w.w);
   }
 
-  const float sc = 1.4426950408889634f / sqrtf(float(D));  // scores in log2 units: exp2 below
+  const float sc = attn_score_scale(D);
   float m = -INFINITY, l = 0.0f;
   f32x4_t ot[DT];
 #pragma unroll
@@ -181,40 +144,21 @@ __global__ void __launch_bounds__(64 * kWaves) attn_partial_kernel(const uint16_
       for (int i = 0; i < DT / 2; ++i) vv[j].w[i] = 0;  // a position behind the length is a zero row, never a load
       if (valid[j]) vv[j].load(vb + int64_t(pv) * D + r * DT);
     }
-    // online softmax for head r over the step
-    float s[8];
-    float mx = -INFINITY;
+    // online softmax for head r over the step; m stays finite: position p0 is valid
+    float s[8], alpha;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s[j] = valid[j] ? st[j >> 2][j & 3] * sc : -INFINITY;
-      mx = fmaxf(mx, s[j]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m, mx);  // finite: position p0 is valid
-    const float alpha = exp2f(m - m_new);
+    for (int j = 0; j < 8; ++j) s[j] = valid[j] ? st[j >> 2][j & 3] * sc : -INFINITY;
     uint32_t pw[4];
-    float psum = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const uint16_t a = f32_to_bf16_rne(exp2f(s[2 * i] - m_new));
-      const uint16_t c = f32_to_bf16_rne(exp2f(s[2 * i + 1] - m_new));
-      psum += bf16_to_f32(a);
-      psum += bf16_to_f32(c);
-      pw[i] = uint32_t(a) | (uint32_t(c) << 16);
-    }
-    l = l * alpha + psum;
-    m = m_new;
+    // through copies: with (m, l) themselves passed, which live across the unrolled loop and its break, the
+    // compiler takes up to 20 VGPRs more (d = 32: 76 for 56) and occupancy drops
+    float mi = m, li = l;
+    attn_softmax_step(s, mi, li, alpha, pw);
+    m = mi, l = li;
     const bf16x8_t pf = as_frag(pw);
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
-      // row r of tile t of V^T: element t of each of the 8 loaded pieces
       uint32_t aw[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const uint32_t lo = vv[2 * i].w[t >> 1], hi = vv[2 * i + 1].w[t >> 1];
-        aw[i] = (t & 1) ? ((lo >> 16) | (hi & 0xFFFF0000u)) : ((lo & 0xFFFFu) | (hi << 16));
-      }
+      attn_vt_row(vv, t, aw);
       ot[t] = ot[t] * alpha;
       ot[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(aw), pf, ot[t], 0, 0, 0);
     }
@@ -313,8 +257,6 @@ hipError_t launch_attn(const uint16_t* q, const uint16_t* k_cache, const uint16_
     attn_combine_kernel<D, false><<<grid, D, 0, s>>>(lens, capacity, heads, p.group, int(p.nchunks), ws_o, ws_ml, y);
   return hipGetLastError();
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

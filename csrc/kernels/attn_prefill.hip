@@ -28,18 +28,15 @@
 // of its pieces) and the fetch's stores (consecutive lanes, consecutive pieces
 // of a row). The epilogue's f32 rows are swizzled the same way by 4-float piece.
 //
-// Scores: S^T = K Q^T on v_mfma_f32_16x16x32_bf16 as in attn_decode.hip - K rows
-// from LDS are the A operand (8 consecutive d of one position a lane), the Q^T
-// fragments the B operand, loaded once and kept in registers. A lane holds
-// scores of ONE query row (lane & 15) per column block: running maximum and sum
-// are per lane, the maximum of a 32-position step costs two xor shuffles. Scores
-// are in log2 units. P is rounded to bf16 and is, as it lies, the B operand of
-// O^T = V^T P^T; the A operand V^T is built in registers from the V tile in LDS
-// with 16-bit packs, as the decode kernel does from global memory.
+// Scores, softmax and output follow the lane map and the numerics of attn_mma.h,
+// which attn_decode.hip shares: S^T = K Q^T with K rows from LDS and the Q^T
+// fragments loaded once and kept in registers, a column a query row of one of
+// the wave's two column blocks; the online softmax per 32-position step; O^T =
+// V^T P^T with V^T built in registers from the V tile in LDS.
 // [Departure from the plan of a transposing LDS read: gfx950's ds_read_b64_tr_b16
 // is exposed by the compiler, but its lane mapping could not be verified on a
 // device while this was written; the packs share one proven mapping with
-// attn_decode.hip.] l is summed from the rounded p; the end is o / l.
+// attn_decode.hip.] The end is o / l.
 //
 // Causality: a 32-position step that crosses the wave's diagonal gets score -inf
 // per lane from the position; a step wholly behind the wave's last row is
@@ -55,9 +52,9 @@
 // strides, or the tile, wave and column it falls into.
 #include <hip/hip_runtime.h>
 
-#include "kernels/attn_prefill_plan.h"
+#include "kernels/attn_mma.h"
+#include "kernels/attn_plan.h"
 #include "kernels/kernels.h"
-#include "kernels/mxfp4_mma.h"
 
 namespace dissem {
 namespace kern {
@@ -66,8 +63,6 @@ namespace {
 
 constexpr int BQ = kAttnPrefillBQ, BK = kAttnPrefillBK, kThreads = kAttnPrefillThreads, kWaves = 4;
 static_assert(BQ == 32 * kWaves && BK == 64 && kThreads == 64 * kWaves, "the work split below");
-
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(uint32_t(h) << 16); }
 
 // Element offset of 16-byte piece `piece` of row `row` of a [BK][D] bf16 tile in LDS.
 template <int D>
@@ -82,30 +77,6 @@ __device__ __forceinline__ int o_off(int row, int dd) {
   constexpr int SH = D == 32 ? 1 : 0, MASK = D == 32 ? 7 : 15;
   return row * D + 4 * ((dd >> 2) ^ ((row >> SH) & MASK)) + (dd & 3);
 }
-
-template <int N>
-struct Words;
-template <>
-struct Words<4> {
-  uint32_t w[4];
-  __device__ __forceinline__ void load(const uint16_t* p) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    w[0] = u.x, w[1] = u.y, w[2] = u.z, w[3] = u.w;
-  }
-};
-template <>
-struct Words<2> {
-  uint32_t w[2];
-  __device__ __forceinline__ void load(const uint16_t* p) {
-    const uint2 u = *reinterpret_cast<const uint2*>(p);
-    w[0] = u.x, w[1] = u.y;
-  }
-};
-template <>
-struct Words<1> {
-  uint32_t w[1];
-  __device__ __forceinline__ void load(const uint16_t* p) { w[0] = *reinterpret_cast<const uint32_t*>(p); }
-};
 
 // ---------------------------------------------------------------- attn_prefill
 template <int D, bool BF16>
@@ -160,7 +131,7 @@ __global__ void __launch_bounds__(kThreads) attn_prefill_kernel(
     }
   }
 
-  const float sc = 1.4426950408889634f / sqrtf(float(D));  // scores in log2 units: exp2 below
+  const float sc = attn_score_scale(D);
   float m[2] = {-INFINITY, -INFINITY}, l[2] = {0.0f, 0.0f};
   f32x4_t ot[2][DT];
 #pragma unroll
@@ -234,36 +205,14 @@ __global__ void __launch_bounds__(kThreads) attn_prefill_kernel(
           for (int j = 0; j < 8; ++j)
             if (p0 + 16 * (j >> 2) + 4 * g + (j & 3) > prow[cb]) s[j] = -INFINITY;
         }
-        float mx = s[0];
-#pragma unroll
-        for (int j = 1; j < 8; ++j) mx = fmaxf(mx, s[j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m[cb], mx);  // finite: the first step holds position 0, which every row sees
-        alpha[cb] = exp2f(m[cb] - m_new);
-        uint32_t pw[4];
-        float psum = 0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint16_t a = f32_to_bf16_rne(exp2f(s[2 * i] - m_new));
-          const uint16_t c = f32_to_bf16_rne(exp2f(s[2 * i + 1] - m_new));
-          psum += bf16_to_f32(a);
-          psum += bf16_to_f32(c);
-          pw[i] = uint32_t(a) | (uint32_t(c) << 16);
-        }
-        l[cb] = l[cb] * alpha[cb] + psum;
-        m[cb] = m_new;
+        uint32_t pw[4];  // m stays finite: the first step holds position 0, which every row sees
+        attn_softmax_step(s, m[cb], l[cb], alpha[cb], pw);
         pf[cb] = as_frag(pw);
       }
 #pragma unroll
       for (int tv = 0; tv < DT; ++tv) {
-        // row r of tile tv of V^T: element tv of each of the 8 pieces
         uint32_t aw[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t lo = vv[2 * i].w[tv >> 1], hi = vv[2 * i + 1].w[tv >> 1];
-          aw[i] = (tv & 1) ? ((lo >> 16) | (hi & 0xFFFF0000u)) : ((lo & 0xFFFFu) | (hi << 16));
-        }
+        attn_vt_row(vv, tv, aw);
         const bf16x8_t af = as_frag(aw);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
@@ -409,8 +358,6 @@ hipError_t launch_rope_seq(const uint16_t* q, int64_t ldq, const uint16_t* k, in
                                                                    capacity, heads, kv_heads, q_out, k_cache, v_cache);
   return hipGetLastError();
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

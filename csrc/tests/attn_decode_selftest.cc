@@ -1,5 +1,5 @@
 // attn_decode_selftest: the host-side sizing of the single-token attention
-// (kernels/attn_decode_plan.h) under Address and UndefinedBehavior sanitizer
+// (kernels/attn_plan.h) under Address and UndefinedBehavior sanitizer
 // (make sanitize-attn). No GPU and no HIP:
 //   * for small shapes the workspace is a heap allocation of exactly
 //     plan.ws_bytes and every index the two kernels form - partial row
@@ -15,7 +15,7 @@
 #include <cstdio>
 #include <memory>
 
-#include "kernels/attn_decode_plan.h"
+#include "kernels/attn_plan.h"
 
 using namespace dissem::kern;
 
@@ -75,7 +75,7 @@ int main() {
 
   // the extremes of the contract
   {
-    const int64_t cap = kAttnMaxCapacity;
+    const int64_t cap = kAttnMaxPositions;
     AttnDecodePlan p = attn_decode_plan(64, 128, 8, 128, cap, cap);  // 4096 chunks of 64 * 8 (b, head)
     EXPECT(p.ok && p.nchunks == 4096 && p.blocks == int64_t(64) * 8 * 4096 && p.group == 16);
     EXPECT(p.ws_bytes == p.blocks * 16 * 130 * 4);
@@ -102,7 +102,7 @@ int main() {
   EXPECT(!attn_decode_plan(1, 4, 0, 64, C, C).ok);
   EXPECT(!attn_decode_plan(1, 4, 2, 64, C, C + 1).ok);  // max_len > capacity
   EXPECT(!attn_decode_plan(1, 4, 2, 64, C, 0).ok);
-  EXPECT(!attn_decode_plan(1, 4, 2, 64, kAttnMaxCapacity + 1, 1).ok);
+  EXPECT(!attn_decode_plan(1, 4, 2, 64, kAttnMaxPositions + 1, 1).ok);
   EXPECT(!attn_decode_plan(INT64_MAX, 4, 2, 64, C, C).ok);
   EXPECT(!attn_decode_plan(1, INT64_MAX, INT64_MAX, 64, C, C).ok);
   EXPECT(!attn_decode_plan(int64_t(1) << 30, 1 << 20, 1 << 16, 64, C, C).ok);

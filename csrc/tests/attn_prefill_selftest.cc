@@ -1,5 +1,5 @@
 // attn_prefill_selftest: the host-side sizing of the prefill attention and of the
-// many-token rope (kernels/attn_prefill_plan.h) under ASan + UBSan (make
+// many-token rope (kernels/attn_plan.h) under ASan + UBSan (make
 // sanitize-attn-prefill), no GPU: every workgroup of the plan's grid marks, with
 // the kernel's own index arithmetic, its rows of an exact-size y (a row outside
 // is an ASan report, one served twice or never a failure); the contract's
@@ -8,7 +8,7 @@
 #include <cstdio>
 #include <memory>
 
-#include "kernels/attn_prefill_plan.h"
+#include "kernels/attn_plan.h"
 
 using namespace dissem::kern;
 
@@ -38,7 +38,7 @@ static void walk(int64_t B, int64_t S, int64_t heads, int64_t kv_heads, int64_t 
 }
 
 int main() {
-  const int64_t BQ = kAttnPrefillBQ, T = kAttnPrefillMaxT, M = kAttnPrefillMaxStride;
+  const int64_t BQ = kAttnPrefillBQ, T = kAttnMaxPositions, M = kAttnPrefillMaxStride;
   for (int64_t d : {32, 64, 128})
     for (int64_t group : {1, 3, 8})
       for (int64_t S : {int64_t(1), BQ, BQ + 1, 2 * BQ + 3}) walk(3, S, 2 * group, 2, d);

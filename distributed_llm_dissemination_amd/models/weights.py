@@ -339,6 +339,15 @@ def _gated(h: torch.Tensor, wg: Param, wu: Param, fuse: bool, fuse_gated: bool =
     return F.silu(_linear(h, wg, tiled, act)) * _linear(h, wu, tiled, act)
 
 
+def _attn_tail(x: torch.Tensor, a: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fuse: bool, fuse_gated: bool,
+               tiled: bool, act: Optional[str]) -> torch.Tensor:
+    """The layer behind its attention `a`: o_proj and the residual `x`, the second norm, the gated MLP, its residual."""
+    x = x + _linear(a, p["o_proj"], tiled, act)
+    h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
+    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled, act), p["down_proj"], tiled,
+                       act)
+
+
 def _rope_tables(capacity: int, d: int, theta: float, device) -> Tuple[torch.Tensor, torch.Tensor]:
     """cos and sin [capacity, d] of `_rope` for positions 0 .. capacity - 1: the same
     expressions on the same device, so row t holds the bits `_rope` uses at position t."""
@@ -459,10 +468,7 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
         elif cache is not None:
             cache.lens.fill_(s)
             cache.max_len = s
-        x = x + _linear(a, p["o_proj"], tiled, act)
-        h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-        return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled, act), p["down_proj"],
-                           tiled, act)
+        return _attn_tail(x, a, p, spec, fuse, fuse_gated, tiled, act)
     q = q.view(b, s, nh, hd).transpose(1, 2)
     k = k.view(b, s, nkv, hd).transpose(1, 2)
     v = v.view(b, s, nkv, hd).transpose(1, 2)
@@ -475,10 +481,7 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     k = k.repeat_interleave(nh // nkv, dim=1)
     v = v.repeat_interleave(nh // nkv, dim=1)
     a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-    x = x + _linear(a.transpose(1, 2).reshape(b, s, nh * hd), p["o_proj"], tiled, act)
-    h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, tiled, act), p["down_proj"], tiled,
-                       act)
+    return _attn_tail(x, a.transpose(1, 2).reshape(b, s, nh * hd), p, spec, fuse, fuse_gated, tiled, act)
 
 
 def _check_cache(cache: KVCache, spec: DecoderSpec, batch: int, device: torch.device) -> None:
@@ -522,7 +525,4 @@ def decoder_step(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, cache:
     if advance:
         cache.lens.add_(1)
         cache.max_len += 1
-    x = x + _linear(a.view(b, 1, spec.heads * spec.head_dim), p["o_proj"], False, act)
-    h = _rms_norm(x, _dense(p["post_attention_layernorm"]), spec.eps)
-    return x + _linear(_gated(h, p["gate_proj"], p["up_proj"], fuse, fuse_gated, False, act), p["down_proj"], False,
-                       act)
+    return _attn_tail(x, a.view(b, 1, spec.heads * spec.head_dim), p, spec, fuse, fuse_gated, False, act)

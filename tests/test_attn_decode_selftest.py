@@ -1,4 +1,4 @@
-"""The host-side sizing of ops.attn_decode (csrc/kernels/attn_decode_plan.h: the checks, the grid
+"""The host-side sizing of ops.attn_decode (csrc/kernels/attn_plan.h: the checks, the grid
 and the workspace of a launch) under Address and UndefinedBehavior sanitizer: `make sanitize-attn`
 builds csrc/tests/attn_decode_selftest.cc (a stand-alone program, no GPU) with
 -fsanitize=address,undefined and runs it. The program walks an exact-size workspace with the two

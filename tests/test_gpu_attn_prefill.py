@@ -10,7 +10,8 @@ condition that makes the bound see a lost position.
    doubled with other garbage; K / V as strided slices of a merged-projection buffer; causality at j0.
 3. rope_append_seq against `_rope` on the GPU, bit for bit, and nothing else of the caches touched.
 4. decoder_forward(attn="mfma"), extend and a decoder_step behind it against the float64 ref_decoder.
-5. Errors: ValueError before any launch."""
+5. Errors: ValueError before any launch.
+6. A row of exactly one 32-position step has ops.attn_decode's bits (both take the step from attn_mma.h)."""
 import numpy as np
 import pytest
 import torch
@@ -91,6 +92,28 @@ def test_merged_projection_slices_and_causality(batch):
         first = max(j0[b] - st, 0)  # the first row that sees j0
         assert same_bits(y3[b, :first], y32[b, :first]), b
         assert all(not same_bits(y3[b, i], y32[b, i]) for i in range(first, s)), b
+
+
+@pytest.mark.parametrize("d", [32, 64, 128])
+def test_one_step_is_attn_decode_bit_for_bit(gpu, d):
+    """Both kernels take their softmax step from attn_mma.h, so a row that needs exactly one 32-position step
+    has attn_decode's bits: every length 1..32 (slot 0; the other two slots run through them in other orders),
+    the query of the last position, f32. Decode's wave merge and chunk combine then multiply by exp2(0) = 1
+    and add exact zeros, and both end in one f32 division by l. Behind a length the caches hold NaN and inf
+    patterns, which neither kernel loads."""
+    b, kvh, group, cap = 3, 2, 4, 64
+    g = torch.Generator().manual_seed(d)
+    q = torch.randn(b, kvh * group, d, generator=g).to(torch.bfloat16).cuda()
+    k, v = (torch.randn(b, kvh, cap, d, generator=g).to(torch.bfloat16).cuda() for _ in range(2))
+    gk, gv = garbage(k.shape, 61).cuda(), garbage(k.shape, 62).cuda()
+    pos = torch.arange(cap, device="cuda")[None, None, :, None]
+    for n in range(1, 33):
+        lens = torch.tensor([n, 33 - n, (n + 10) % 32 + 1], dtype=torch.int32, device="cuda")
+        valid = pos < lens[:, None, None, None]
+        kc, vc = torch.where(valid, k, gk), torch.where(valid, v, gv)
+        yd = ops.attn_decode(q, kc, vc, lens, out_dtype=torch.float32)
+        yp = ops.attn_prefill(q[:, None], kc, vc, lens - 1, out_dtype=torch.float32)
+        assert same_bits(yp[:, 0], yd), (d, n)
 
 
 @pytest.mark.parametrize("merged", [True, False], ids=["merged", "separate"])
