@@ -81,8 +81,6 @@ __global__ void __launch_bounds__(64 * kWaves) attn_partial_kernel(const uint16_
                                                                    float* __restrict__ ws_o, float* __restrict__ ws_ml) {
   constexpr int KS = D / 32;  // MFMA k steps of q . k
   constexpr int DT = D / 16;  // 16-row tiles of V^T; also the d a lane loads of a V row
-  __shared__ float sm_o[kWaves][16][D];
-  __shared__ float sm_m[kWaves][16], sm_l[kWaves][16];
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 15, g = lane >> 4;
@@ -163,41 +161,7 @@ __global__ void __launch_bounds__(64 * kWaves) attn_partial_kernel(const uint16_
       ot[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(aw), pf, ot[t], 0, 0, 0);
     }
   }
-  // the lane groups' partial sums of l, the same value in all four
-  l += __shfl_xor(l, 16);
-  l += __shfl_xor(l, 32);
-
-  // accumulator register i of tile t: row 4 g + i of the tile, d = (4 g + i) * DT + t; column r is the head
-#pragma unroll
-  for (int t = 0; t < DT; ++t)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) sm_o[wave][r][(4 * g + i) * DT + t] = ot[t][i];
-  if (g == 0) {
-    sm_m[wave][r] = m;
-    sm_l[wave][r] = l;
-  }
-  __syncthreads();
-
-  // the four waves in wave order; wave 0 always had a valid step, so the maximum is finite
-  for (int idx = threadIdx.x; idx < group * D; idx += 64 * kWaves) {
-    const int h = idx / D, dd = idx % D;
-    float mm = sm_m[0][h];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) mm = fmaxf(mm, sm_m[w][h]);
-    float o = 0.0f, ll = 0.0f;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const float f = exp2f(sm_m[w][h] - mm);  // a wave without a step: exp2(-inf) = 0 times its zeros
-      o += f * sm_o[w][h][dd];
-      ll += f * sm_l[w][h];
-    }
-    const int64_t row = blk * group + h;
-    ws_o[row * D + dd] = o;
-    if (dd == 0) {
-      ws_ml[row * 2] = mm;
-      ws_ml[row * 2 + 1] = ll;
-    }
-  }
+  attn_merge_waves<D, kWaves>(m, l, ot, group, blk, ws_o, ws_ml);
 }
 
 template <int D, bool BF16>
@@ -248,17 +212,29 @@ hipError_t launch_attn(const uint16_t* q, const uint16_t* k_cache, const uint16_
   float* ws_ml = ws + p.o_floats;
   attn_partial_kernel<D><<<unsigned(p.blocks), 64 * kWaves, 0, s>>>(q, k_cache, v_cache, lens, capacity, heads,
                                                                     kv_heads, p.group, int(p.nchunks), ws_o, ws_ml);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
+  return attn_decode_combine(D, lens, B, heads, capacity, p.group, int(p.nchunks), ws_o, ws_ml, y, y_bf16, s);
+}
+
+template <int D>
+hipError_t launch_combine(const int32_t* lens, int64_t B, int heads, int capacity, int group, int nchunks,
+                          const float* ws_o, const float* ws_ml, void* y, bool y_bf16, hipStream_t s) {
   const unsigned grid = unsigned(B * heads);
-  if (y_bf16)
-    attn_combine_kernel<D, true><<<grid, D, 0, s>>>(lens, capacity, heads, p.group, int(p.nchunks), ws_o, ws_ml, y);
-  else
-    attn_combine_kernel<D, false><<<grid, D, 0, s>>>(lens, capacity, heads, p.group, int(p.nchunks), ws_o, ws_ml, y);
+  if (y_bf16) attn_combine_kernel<D, true><<<grid, D, 0, s>>>(lens, capacity, heads, group, nchunks, ws_o, ws_ml, y);
+  else attn_combine_kernel<D, false><<<grid, D, 0, s>>>(lens, capacity, heads, group, nchunks, ws_o, ws_ml, y);
   return hipGetLastError();
 }
 
 }  // namespace
+
+hipError_t attn_decode_combine(int d, const int32_t* lens, int64_t B, int heads, int capacity, int group,
+                               int nchunks, const float* ws_o, const float* ws_ml, void* y, bool y_bf16,
+                               hipStream_t s) {
+  if (d == 32) return launch_combine<32>(lens, B, heads, capacity, group, nchunks, ws_o, ws_ml, y, y_bf16, s);
+  if (d == 64) return launch_combine<64>(lens, B, heads, capacity, group, nchunks, ws_o, ws_ml, y, y_bf16, s);
+  return launch_combine<128>(lens, B, heads, capacity, group, nchunks, ws_o, ws_ml, y, y_bf16, s);
+}
 
 hipError_t attn_rope_append(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
                             int64_t ldv, const int32_t* pos, const float* cos, const float* sin, int64_t B,

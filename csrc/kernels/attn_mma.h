@@ -1,6 +1,7 @@
-// Device code shared by the two attention kernels (attn_decode.hip,
-// attn_prefill.hip): the straight-line pieces between their own loads and
-// epilogues, so that both have one set of numerics. All of internal linkage.
+// Device code shared by the attention kernels (attn_decode.hip,
+// attn_decode_mxfp8.hip, attn_prefill.hip): the straight-line pieces between
+// their own loads and epilogues, so that all have one set of numerics. All of
+// internal linkage, except the declaration of the decode kernels' shared combine launch.
 //
 // Both kernels run a 32-position step of one KV head on v_mfma_f32_16x16x32_bf16
 // with the same lane map (r = lane & 15, g = lane >> 4):
@@ -27,13 +28,19 @@
 
 #include <cstdint>
 
+#include "kernels/bf16_bits.h"
 #include "kernels/mxfp4_mma.h"
 
 namespace dissem {
 namespace kern {
-namespace {
 
-__device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(uint32_t(h) << 16); }
+// attn_decode.hip's second launch, which merges the chunk partials (m, l, o) of the workspace in ascending
+// chunk order into y; the MXFP8 attention (attn_decode_mxfp8.hip) ends with the same launch.
+hipError_t attn_decode_combine(int d, const int32_t* lens, int64_t B, int heads, int capacity, int group,
+                               int nchunks, const float* ws_o, const float* ws_ml, void* y, bool y_bf16,
+                               hipStream_t s);
+
+namespace {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -98,6 +105,54 @@ __device__ __forceinline__ void attn_vt_row(const Words<N> (&vv)[8], int t, uint
   for (int i = 0; i < 4; ++i) {
     const uint32_t lo = vv[2 * i].w[t >> 1], hi = vv[2 * i + 1].w[t >> 1];
     aw[i] = (t & 1) ? ((lo >> 16) | (hi & 0xFFFF0000u)) : ((lo & 0xFFFFu) | (hi << 16));
+  }
+}
+
+// The end of a single-token attention workgroup of WAVES waves (attn_decode.hip, attn_decode_mxfp8.hip): the
+// waves' (m, l, ot) of the KV head's group meet in LDS and are merged in wave order into the partial rows
+// blk * group + h of the workspace. Every thread of the workgroup calls it; wave 0 always had a valid step,
+// so the maximum is finite.
+template <int D, int WAVES>
+__device__ __forceinline__ void attn_merge_waves(float m, float l, const f32x4_t (&ot)[D / 16], int group,
+                                                 int64_t blk, float* __restrict__ ws_o, float* __restrict__ ws_ml) {
+  constexpr int DT = D / 16;
+  __shared__ float sm_o[WAVES][16][D];
+  __shared__ float sm_m[WAVES][16], sm_l[WAVES][16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  // the lane groups' partial sums of l, the same value in all four
+  l += __shfl_xor(l, 16);
+  l += __shfl_xor(l, 32);
+
+  // accumulator register i of tile t: row 4 g + i of the tile, d = (4 g + i) * DT + t; column r is the head
+#pragma unroll
+  for (int t = 0; t < DT; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sm_o[wave][r][(4 * g + i) * DT + t] = ot[t][i];
+  if (g == 0) {
+    sm_m[wave][r] = m;
+    sm_l[wave][r] = l;
+  }
+  __syncthreads();
+
+  for (int idx = threadIdx.x; idx < group * D; idx += 64 * WAVES) {
+    const int h = idx / D, dd = idx % D;
+    float mm = sm_m[0][h];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) mm = fmaxf(mm, sm_m[w][h]);
+    float o = 0.0f, ll = 0.0f;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      const float f = exp2f(sm_m[w][h] - mm);  // a wave without a step: exp2(-inf) = 0 times its zeros
+      o += f * sm_o[w][h][dd];
+      ll += f * sm_l[w][h];
+    }
+    const int64_t row = blk * group + h;
+    ws_o[row * D + dd] = o;
+    if (dd == 0) {
+      ws_ml[row * 2] = mm;
+      ws_ml[row * 2 + 1] = ll;
+    }
   }
 }
 

@@ -1,6 +1,6 @@
-// Host-side sizing of the single-token attention and rope (attn_decode.hip) and
-// of the causal prefill / extend attention and many-token rope (attn_prefill.hip):
-// the shape and stride checks, the tile constants, the grids and the workspace as
+// Host-side sizing of the single-token attention and rope (attn_decode.hip; on
+// an MXFP8 cache attn_decode_mxfp8.hip) and of the causal prefill / extend
+// attention and many-token rope (attn_prefill.hip): the shape and stride checks, the tile constants, the grids and the workspace as
 // plain integer arithmetic, with no HIP in it, so that stand-alone programs can run it
 // under a sanitizer (csrc/tests/attn_decode_selftest.cc, attn_prefill_selftest.cc).
 #pragma once
@@ -84,6 +84,43 @@ inline bool attn_rope_plan(int64_t B, int64_t heads, int64_t kv_heads, int64_t d
                            int64_t ldk, int64_t ldv) {
   if (B < 1 || B > 0x7FFFFFFF || !attn_rope_rows_ok(B, heads, kv_heads, d, capacity, ldq, ldk, ldv)) return false;
   return heads + 2 * kv_heads <= 65535;  // grid.y
+}
+
+// ---- the MXFP8 KV cache (attn_decode_mxfp8.hip): e4m3 codes uint8 [B, kv_heads, capacity, d] and one E8M0
+// scale byte per 32 d, uint8 [B, kv_heads, capacity, d / 32].
+
+// d 64 or 128: at d = 32 half a head is half a scale block, which the rope's lane map does not serve.
+inline bool attn_mxfp8_d_ok(int64_t d) { return d == 64 || d == 128; }
+
+// attn_decode_plan for that cache: the same grid and workspace. The codes are B kv_heads capacity d <= 2^31
+// 2^20 2^7 = 2^58 bytes and the scale bytes a 32nd of them, so both tensors' last byte is an int64 offset.
+inline AttnDecodePlan attn_decode_mxfp8_plan(int64_t B, int64_t heads, int64_t kv_heads, int64_t d,
+                                             int64_t capacity, int64_t max_len) {
+  if (!attn_mxfp8_d_ok(d)) return AttnDecodePlan();
+  return attn_decode_plan(B, heads, kv_heads, d, capacity, max_len);
+}
+
+// The MXFP8 rope_append launch: an item is one thread's work, a (head of q, k or v, piece of 8 d of the
+// lower half with its partners of the upper half); workgroup (b, y) takes items [y * kAttnRopeMxThreads, ...)
+// of sequence b. Rows are read 16 bytes at a time: ldq, ldk and ldv are multiples of 8 elements.
+constexpr int kAttnRopeMxThreads = 256;
+
+struct AttnRopeMxPlan {
+  bool ok = false;
+  int items = 0;   // (heads + 2 kv_heads) * (d / 16) <= 3 * 65535 * 8
+  int grid_y = 0;  // workgroups of a sequence
+};
+
+inline AttnRopeMxPlan attn_rope_mxfp8_plan(int64_t B, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity,
+                                           int64_t ldq, int64_t ldk, int64_t ldv) {
+  AttnRopeMxPlan p;
+  if (!attn_mxfp8_d_ok(d) || B < 1 || B > 0x7FFFFFFF) return p;
+  if (!attn_rope_rows_ok(B, heads, kv_heads, d, capacity, ldq, ldk, ldv)) return p;
+  if (ldq % 8 || ldk % 8 || ldv % 8) return p;
+  p.items = int((heads + 2 * kv_heads) * (d / 16));
+  p.grid_y = (p.items + kAttnRopeMxThreads - 1) / kAttnRopeMxThreads;  // <= 6144
+  p.ok = true;
+  return p;
 }
 
 struct AttnPrefillPlan {

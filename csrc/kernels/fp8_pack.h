@@ -8,13 +8,12 @@
 
 #include <cstdint>
 
+#include "kernels/bf16_bits.h"
 #include "kernels/dpp.h"
 
 namespace dissem {
 namespace kern {
 namespace {
-
-__device__ inline float bf16_to_f32(uint16_t b) { return __uint_as_float(uint32_t(b) << 16); }
 
 // E of the block scale 2^E from the block's finite amax: core/fp8.h scale_exp.
 __device__ inline int scale_exp(uint32_t amax_bits) {

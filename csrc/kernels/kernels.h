@@ -345,6 +345,40 @@ hipError_t attn_decode(const uint16_t* q, const uint16_t* k_cache, const uint16_
                        int64_t B, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, int64_t max_len,
                        void* ws, int64_t ws_bytes, void* y, bool y_bf16, hipStream_t s);
 
+// ---- attn_decode_mxfp8.hip: the same step against an MXFP8 KV cache (core/mxfp8_act.h's format): per
+// cache OCP e4m3fn codes uint8 [B, kv_heads, capacity, d] and E8M0 scale bytes uint8 [B, kv_heads, capacity,
+// d / 32], block j of a row elements [32 j, 32 j + 32) along d; both contiguous, the codes 16-B and the scale
+// bytes 4-B aligned. d 64 or 128 only; every other limit is attn_decode's.
+//   Dequantization: code * 2^(byte - 127), rounded to bf16 to nearest even (fp8x2_to_bf16x2). That is exact
+// except where the product falls between bf16 subnormals, which takes a subnormal code at a byte of 3 or less.
+//   Result: attn_decode's on that dequantized cache - f32 scores, online softmax per 32 positions, P rounded
+// to bf16, the same chunks, workspace (attn_decode_workspace_bytes) and combine launch. Bit equality with
+// attn_decode is NOT promised: K's d sit in other k slots of the MFMA, so a score's f32 sum has another order.
+//   Invariance: a row's bits do not depend on the batch, the slot, the capacity or max_len, as in attn_decode.
+//   Scale bytes: the quantizer writes [1, 247]. A byte of 255 or a NaN code (0x7F / 0xFF) inside the valid
+// prefix makes the rows of that (b, KV head)'s query heads NaN - in K every element of them, a zero code
+// under a byte of 255 included; in V the d of the code, or the 32 d of the byte's block - and leaves every
+// other row its bits (scripts/attn_decode_mxfp8_nonfinite.py prints it). A byte of 0 is outside the contract:
+// the value is unspecified, and no access leaves the tensors. No code and no scale byte at or behind lens[b]
+// is ever loaded; lens outside the promise are clamped as in attn_decode.
+//
+// attn_rope_append_mxfp8, ONE launch: attn_rope_append into such a cache. q_out is attn_rope_append's, bit
+// for bit; k is rotated and rounded to bf16, then quantized, v is quantized as it is: the bytes written are
+// mxfp8::quantize_host of the bf16 rows attn_rope_append would have written. q, k, v as there, with ldq, ldk
+// and ldv multiples of 8 on 16-byte-aligned bases (16-byte loads), cos and sin 16-B aligned. A pos[b] outside
+// [0, capacity) writes nothing to the four cache tensors and a zero q_out row. A thread rotates 8 d of the
+// lower half of a head and their partners of the upper half; four adjacent lanes quantize a 32-block.
+// Anything else: hipErrorInvalidValue, before any launch.
+hipError_t attn_rope_append_mxfp8(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk, const uint16_t* v,
+                                  int64_t ldv, const int32_t* pos, const float* cos, const float* sin, int64_t B,
+                                  int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, uint16_t* q_out,
+                                  uint8_t* k_codes, uint8_t* k_scales, uint8_t* v_codes, uint8_t* v_scales,
+                                  hipStream_t s);
+hipError_t attn_decode_mxfp8(const uint16_t* q, const uint8_t* k_codes, const uint8_t* k_scales,
+                             const uint8_t* v_codes, const uint8_t* v_scales, const int32_t* lens, int64_t B,
+                             int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, int64_t max_len, void* ws,
+                             int64_t ws_bytes, void* y, bool y_bf16, hipStream_t s);
+
 // ---- attn_prefill.hip: causal attention of S new tokens per sequence against K
 // and V in HBM (prefill, chunked prefill, multi-token extend), and their rope
 // and cache append.

@@ -120,6 +120,20 @@ int main() {
   EXPECT(!attn_rope_plan(3, 4, 2, 64, 16, INT64_MAX, 128, 128));
   EXPECT(!attn_rope_plan(INT64_MAX, INT64_MAX, INT64_MAX, 64, 16, 512, 128, 128));
 
+  // the MXFP8 cache: attn_decode_plan's grid and workspace for d 64 and 128 alone; the rope's items and grid
+  EXPECT(!attn_decode_mxfp8_plan(3, 4, 2, 32, C, C).ok);
+  EXPECT(attn_decode_mxfp8_plan(3, 4, 2, 64, C, C).ws_bytes == attn_decode_plan(3, 4, 2, 64, C, C).ws_bytes);
+  EXPECT(attn_decode_mxfp8_plan(64, 128, 8, 128, kAttnMaxPositions, kAttnMaxPositions).blocks == int64_t(64) * 8 * 4096);
+  {
+    AttnRopeMxPlan p = attn_rope_mxfp8_plan(3, 30, 3, 128, 16, 30 * 128, 3 * 128, 3 * 128);
+    EXPECT(p.ok && p.items == 288 && p.grid_y == 2);
+    p = attn_rope_mxfp8_plan(3, 65535, 65535, 128, 16, int64_t(65535) * 128, int64_t(65535) * 128, int64_t(65535) * 128);
+    EXPECT(p.ok && p.items == 3 * 65535 * 8 && p.grid_y == 6144);
+    EXPECT(!attn_rope_mxfp8_plan(3, 4, 2, 32, 16, 128, 64, 64).ok);   // d
+    EXPECT(!attn_rope_mxfp8_plan(3, 4, 2, 64, 16, 260, 128, 128).ok);  // a row stride that 16-byte loads do not fit
+    EXPECT(!attn_rope_mxfp8_plan(int64_t(1) << 31, 4, 2, 64, 16, 256, 128, 128).ok);
+  }
+
   if (failures) {
     fprintf(stderr, "attn_decode_selftest: %d failure(s)\n", failures);
     return 1;

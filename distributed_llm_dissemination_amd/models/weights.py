@@ -363,7 +363,11 @@ class KVCache:
     capacity, head_dim] (k rotated), `lens` int32 [batch] on their device - positions
     [0, lens[b]) of sequence b are valid, whatever lies behind is never read - the
     rotary tables `cos`, `sin` f32 [capacity, head_dim], and `max_len`, a host upper
-    bound of `lens` that sizes the attention's grid without a device round trip."""
+    bound of `lens` that sizes the attention's grid without a device round trip.
+    An MXFP8 cache (`kv_format="mxfp8"`, head_dim 64 or 128) holds in `k` and `v` the
+    uint8 e4m3fn codes of those values and in `k_scale` and `v_scale` one uint8 E8M0 byte
+    per 32 of them, [batch, kv_heads, capacity, head_dim // 32]: 33/64 of the bytes at
+    head_dim 128, the value ``code * 2**(byte - 127)`` (ops.attn_decode has the contract)."""
     k: torch.Tensor
     v: torch.Tensor
     lens: torch.Tensor
@@ -371,14 +375,21 @@ class KVCache:
     sin: torch.Tensor
     capacity: int
     max_len: int = 0
+    k_scale: Optional[torch.Tensor] = None
+    v_scale: Optional[torch.Tensor] = None
 
     @classmethod
     def allocate(cls, spec: DecoderSpec, batch: int, capacity: int, device="cpu",
-                 lens: Optional[torch.Tensor] = None) -> "KVCache":
+                 lens: Optional[torch.Tensor] = None, kv_format: str = "bf16") -> "KVCache":
         """An empty cache: K and V uninitialised, lengths zero. `lens` (int32 [batch] on
-        `device`) lets the layers of a model share one length tensor."""
+        `device`) lets the layers of a model share one length tensor. `kv_format` is
+        "bf16" or "mxfp8"."""
         if batch < 1 or capacity < 1:
             raise ValueError("batch and capacity must be positive")
+        if kv_format not in ("bf16", "mxfp8"):
+            raise ValueError(f"kv_format must be 'bf16' or 'mxfp8', got {kv_format!r}")
+        if kv_format == "mxfp8" and spec.head_dim not in (64, 128):
+            raise ValueError(f"an MXFP8 cache needs a head_dim of 64 or 128, got {spec.head_dim}")
         device = torch.device(device)
         if lens is None:
             lens = torch.zeros(batch, dtype=torch.int32, device=device)
@@ -386,6 +397,10 @@ class KVCache:
             raise ValueError(f"lens must be an int32 [{batch}] tensor on {device}")
         shape = (batch, spec.kv_heads, capacity, spec.head_dim)
         cos, sin = _rope_tables(capacity, spec.head_dim, spec.rope_theta, device)
+        if kv_format == "mxfp8":
+            k, v, ks, vs = (torch.empty(shape[:3] + (n,), dtype=torch.uint8, device=device)
+                            for n in (spec.head_dim, spec.head_dim, spec.head_dim // 32, spec.head_dim // 32))
+            return cls(k, v, lens, cos, sin, capacity, 0, ks, vs)
         return cls(torch.empty(shape, dtype=torch.bfloat16, device=device),
                    torch.empty(shape, dtype=torch.bfloat16, device=device), lens, cos, sin, capacity, 0)
 
@@ -433,13 +448,22 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     attend to all of them - chunked prefill and multi-token extend. `cache.lens` advances
     by seq on the device and `cache.max_len` by seq; ValueError when max_len + seq exceeds
     the capacity. Without `extend` a pass with a cache writes positions [0, seq) and sets
-    lens = seq, as above."""
+    lens = seq, as above.
+    An MXFP8 `cache` (``KVCache.allocate(..., kv_format="mxfp8")``) is prefilled on the
+    default attention route alone: the rotated k, and v, of positions [0, seq) are quantized
+    into it with ``ops.mxfp8_quantize_rows`` - the bytes a sequence of `decoder_step`s would
+    have written - while the pass attends on the fresh bf16 k and v, so its result is that
+    without a cache. `attn="mfma"` or `extend=True` with such a cache raises ValueError: a
+    prefill kernel that reads this format and a ``rope_append_seq`` that writes it do not
+    exist yet."""
     if act not in (None, "mxfp8"):
         raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
     if attn not in (None, "mfma"):
         raise ValueError(f"attn must be None or 'mfma', got {attn!r}")
     if extend and (cache is None or attn != "mfma"):
         raise ValueError("extend=True needs a cache and attn='mfma'")
+    if attn == "mfma" and cache is not None and cache.k_scale is not None:
+        raise ValueError("attn='mfma' and extend=True do not serve an MXFP8 cache: prefill it on the default route")
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     if cache is not None:
@@ -473,9 +497,15 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     k = k.view(b, s, nkv, hd).transpose(1, 2)
     v = v.view(b, s, nkv, hd).transpose(1, 2)
     q, k = _rope(q, spec.rope_theta), _rope(k, spec.rope_theta)
-    if cache is not None:
+    if cache is not None and cache.k_scale is not None:
+        from ..ops import mxfp8_quantize_rows
+
+        cache.k[:, :, :s], cache.k_scale[:, :, :s] = mxfp8_quantize_rows(k.to(torch.bfloat16))
+        cache.v[:, :, :s], cache.v_scale[:, :, :s] = mxfp8_quantize_rows(v.to(torch.bfloat16))
+    elif cache is not None:
         cache.k[:, :, :s] = k
         cache.v[:, :, :s] = v
+    if cache is not None:
         cache.lens.fill_(s)
         cache.max_len = s
     k = k.repeat_interleave(nh // nkv, dim=1)
@@ -491,6 +521,8 @@ def _check_cache(cache: KVCache, spec: DecoderSpec, batch: int, device: torch.de
                          f"this batch and spec need {want}")
     if cache.k.device != device:
         raise ValueError(f"the cache is on {cache.k.device}, x on {device}")
+    if (cache.k_scale is None) != (cache.v_scale is None):
+        raise ValueError("an MXFP8 cache holds both k_scale and v_scale")
 
 
 def decoder_step(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, cache: KVCache, fuse: bool = True,
@@ -520,8 +552,9 @@ def decoder_step(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, cache:
 
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
     q, k, v = _qkv(h, p, fuse, False, act)
-    q = rope_append(q, k, v, cache.cos, cache.sin, cache.k, cache.v, cache.lens)
-    a = attn_decode(q, cache.k, cache.v, cache.lens + 1, max_len=cache.max_len + 1, out_dtype=x.dtype)
+    scales = dict(k_scale=cache.k_scale, v_scale=cache.v_scale)  # None for a bf16 cache
+    q = rope_append(q, k, v, cache.cos, cache.sin, cache.k, cache.v, cache.lens, **scales)
+    a = attn_decode(q, cache.k, cache.v, cache.lens + 1, max_len=cache.max_len + 1, out_dtype=x.dtype, **scales)
     if advance:
         cache.lens.add_(1)
         cache.max_len += 1

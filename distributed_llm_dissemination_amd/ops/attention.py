@@ -4,6 +4,10 @@ host references, under the conventions of kernels.py (current stream, every chec
     # one decode step's attention: caches bf16 [B, kv_heads, capacity, d], lens / pos int32 [B] on the device
     q_rot = ops.rope_append(q, k, v, cos, sin, k_cache, v_cache, pos)     # rotate q and k at pos, append k and v
     a = ops.attn_decode(q_rot, k_cache, v_cache, pos + 1)                 # [B, heads * d], K and V read once per KV head
+    # the same against an MXFP8 cache (attn_decode_mxfp8.hip): uint8 codes [B, kv_heads, capacity, d] and uint8
+    # E8M0 scale bytes [B, kv_heads, capacity, d / 32] per cache, passed as k_scale= and v_scale=; d 64 or 128
+    q_rot = ops.rope_append(q, k, v, cos, sin, k_codes, v_codes, pos, k_scale=k_scale, v_scale=v_scale)
+    a = ops.attn_decode(q_rot, k_codes, v_codes, pos + 1, k_scale=k_scale, v_scale=v_scale)
     # S tokens a sequence (prefill, chunked prefill, extend): q/k/v [B, S, heads or kv_heads * d], start int32 [B]
     q_rot = ops.rope_append_seq(q, k, v, cos, sin, k_cache, v_cache, start)   # positions start[b] + i
     a = ops.attn_prefill(q_rot, k_cache, v_cache, start)                      # [B, S, heads * d], causal, reads the cache
@@ -16,19 +20,26 @@ from typing import Optional, Tuple
 import torch
 
 from .. import _core
-from .kernels import _stream
+from .kernels import _mxfp8_values, _stream, mxfp8_quantize_rows
 
 __all__ = ["rope_append", "attn_decode", "rope_append_seq", "attn_prefill"]
 
 _ATTN_D = (32, 64, 128)
+_ATTN_MXFP8_D = (64, 128)
 _ATTN_MAX_CAPACITY = 1 << 20
 
 
-def _check_caches(k_cache: torch.Tensor, v_cache: torch.Tensor) -> Tuple[int, int, int, int]:
-    """(B, kv_heads, capacity, d) of a pair of KV caches, checked."""
+def _check_caches(k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: Optional[torch.Tensor] = None,
+                  v_scale: Optional[torch.Tensor] = None) -> Tuple[int, int, int, int]:
+    """(B, kv_heads, capacity, d) of a pair of KV caches, checked: bf16 caches without scales, or
+    the uint8 codes of MXFP8 caches with the uint8 scale bytes of both."""
+    mx = k_scale is not None or v_scale is not None
+    if mx and (k_scale is None or v_scale is None):
+        raise ValueError("an MXFP8 cache needs both k_scale and v_scale")
+    want = torch.uint8 if mx else torch.bfloat16
     for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
-        if c.dtype != torch.bfloat16:
-            raise ValueError(f"{name} must be {torch.bfloat16}, got {c.dtype}")
+        if c.dtype != want:
+            raise ValueError(f"{name} must be {want} {'with' if mx else 'without'} k_scale and v_scale, got {c.dtype}")
         if c.dim() != 4 or c.numel() == 0:
             raise ValueError(f"{name} must be [B, kv_heads, capacity, d], got {tuple(c.shape)}")
         if not c.is_contiguous():
@@ -38,11 +49,26 @@ def _check_caches(k_cache: torch.Tensor, v_cache: torch.Tensor) -> Tuple[int, in
     if k_cache.shape != v_cache.shape or k_cache.device != v_cache.device:
         raise ValueError("k_cache and v_cache must have one shape and one device")
     b, kvh, cap, d = k_cache.shape
-    if d not in _ATTN_D:
-        raise ValueError(f"head_dim must be one of {_ATTN_D}, got {d}")
+    if d not in (_ATTN_MXFP8_D if mx else _ATTN_D):
+        raise ValueError(f"head_dim must be one of {_ATTN_MXFP8_D if mx else _ATTN_D}, got {d}")
     if cap > _ATTN_MAX_CAPACITY:
         raise ValueError(f"capacity must be at most {_ATTN_MAX_CAPACITY} positions, got {cap}")
+    if mx:
+        for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+            if t.dtype != torch.uint8 or tuple(t.shape) != (b, kvh, cap, d // 32) or t.device != k_cache.device:
+                raise ValueError(f"{name} must be a uint8 [{b}, {kvh}, {cap}, {d // 32}] tensor on the caches' device")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t.is_cuda and t.data_ptr() % 4:
+                raise ValueError(f"{name} must be 4-byte aligned")
     return b, kvh, cap, d
+
+
+def _mxfp8_rows(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """[..., d] codes and [..., d / 32] scale bytes as the bf16 values the kernel multiplies, in f32."""
+    d = codes.shape[-1]
+    vals = _mxfp8_values(codes.reshape(-1, d), scales.reshape(-1, d // 32))
+    return vals.to(torch.bfloat16).float().view(codes.shape)
 
 
 def _check_index(t: torch.Tensor, name: str, b: int, device: torch.device) -> None:
@@ -111,9 +137,11 @@ def _rows_seq(t: torch.Tensor, name: str, b: int, s: int, n: int, device: torch.
 
 
 def _rope_cpu(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-              k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, heads: int) -> torch.Tensor:
+              k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, heads: int,
+              k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The host route of both rope ops: rows [B * S, heads or kv_heads * d] at positions `pos` int64 [B, S].
-    Returns q rotated [B, S, heads, d]."""
+    With scales the bf16 rows go through the host MXFP8 codec into the caches. Returns q rotated
+    [B, S, heads, d]."""
     b, s = pos.shape
     _, kvh, cap, d = k_cache.shape
     ok = (pos >= 0) & (pos < cap)
@@ -126,13 +154,27 @@ def _rope_cpu(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor, cos: torch.T
 
     q_out = torch.where(ok[:, :, None, None], rot(q2, heads), torch.zeros((), dtype=torch.bfloat16))
     bi, si = ok.nonzero(as_tuple=True)
-    k_cache[bi, :, p[bi, si]] = rot(k2, kvh)[bi, si]
-    v_cache[bi, :, p[bi, si]] = v2.reshape(b, s, kvh, d)[bi, si]
+    k_new, v_new = rot(k2, kvh)[bi, si], v2.reshape(b, s, kvh, d)[bi, si]
+    if k_scale is not None and bi.numel():
+        (k_new, ks), (v_new, vs) = mxfp8_quantize_rows(k_new), mxfp8_quantize_rows(v_new)
+        k_scale[bi, :, p[bi, si]] = ks
+        v_scale[bi, :, p[bi, si]] = vs
+    k_cache[bi, :, p[bi, si]] = k_new
+    v_cache[bi, :, p[bi, si]] = v_new
     return q_out
 
 
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """Rows [b, n] for 16-byte loads: `t` itself where its row stride is a multiple of 8 elements on a
+    16-byte-aligned base, else a copy."""
+    if t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous() if not t.is_contiguous() else t.clone()
+
+
 def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor) -> torch.Tensor:
+                k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, *,
+                k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The rotary embedding of one new token per sequence, fused with the cache append.
 
     `q` [B, ..., heads * d], `k` and `v` [B, ..., kv_heads * d] are bf16 rows of B sequences
@@ -146,8 +188,18 @@ def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Te
     once to bf16: the bits plain torch gives for the same expression. A pos[b] outside
     [0, capacity) writes nothing to the caches and gives a zero q row.
     GPU: one launch on the current stream, no synchronization (`pos` is never read on the
-    host). CPU: plain torch."""
-    b, kvh, cap, d = _check_caches(k_cache, v_cache)
+    host). CPU: plain torch.
+    MXFP8 caches (`k_scale` and `v_scale` given; attn_decode_mxfp8.hip): `k_cache` and
+    `v_cache` are the uint8 e4m3fn codes [B, kv_heads, capacity, d], 16-byte aligned, and the
+    scales the uint8 E8M0 bytes [B, kv_heads, capacity, d // 32], one per 32 d, all
+    contiguous; d 64 or 128. The returned q has the bits of the bf16 route; k is rotated and
+    rounded to bf16, then quantized, v is quantized as it is: the bytes written are those of
+    `mxfp8_quantize_rows` (the host codec) of the rows the bf16 route writes, scale bytes in
+    [1, 247]. An out-of-range pos[b] writes nothing to the four tensors. GPU: still one
+    launch, 16-byte loads (rows whose stride or base does not allow them are copied first).
+    bf16 caches with a scale, uint8 caches without both, scales of another shape, dtype,
+    device or layout and d = 32 are ValueErrors before any launch."""
+    b, kvh, cap, d = _check_caches(k_cache, v_cache, k_scale, v_scale)
     dev = k_cache.device
     _check_index(pos, "pos", b, dev)
     _check_rope_tables(cos, sin, cap, d, dev)
@@ -159,8 +211,18 @@ def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Te
         raise ValueError("heads + 2 * kv_heads must fit a grid dimension (65535)")
     q2, k2, v2 = _rows(q, "q", b, heads * d, dev), _rows(k, "k", b, kvh * d, dev), _rows(v, "v", b, kvh * d, dev)
     if not dev.type == "cuda":
-        return _rope_cpu(q2, k2, v2, cos, sin, k_cache, v_cache, pos.long()[:, None], heads).view(b, heads, d)
+        return _rope_cpu(q2, k2, v2, cos, sin, k_cache, v_cache, pos.long()[:, None], heads, k_scale,
+                         v_scale).view(b, heads, d)
     q_out = torch.empty(b, heads, d, dtype=torch.bfloat16, device=dev)
+    if k_scale is not None:
+        if cos.data_ptr() % 16 or sin.data_ptr() % 16:
+            raise ValueError("cos and sin must be 16-byte aligned")
+        q2, k2, v2 = _rows16(q2), _rows16(k2), _rows16(v2)
+        _core.attn_rope_append_mxfp8(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(),
+                                     v2.stride(0), pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), b, heads, kvh, d,
+                                     cap, q_out.data_ptr(), k_cache.data_ptr(), k_scale.data_ptr(),
+                                     v_cache.data_ptr(), v_scale.data_ptr(), _stream())
+        return q_out
     _core.attn_rope_append(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(), v2.stride(0),
                            pos.data_ptr(), cos.data_ptr(), sin.data_ptr(), b, heads, kvh, d, cap, q_out.data_ptr(),
                            k_cache.data_ptr(), v_cache.data_ptr(), _stream())
@@ -168,6 +230,7 @@ def rope_append(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Te
 
 
 def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, lens: torch.Tensor, *,
+                k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                 max_len: Optional[int] = None, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """Grouped-query attention of one query token per sequence against a KV cache:
     row b of the [B, heads * d] result is, per head h, ``softmax(q[b, h] @ K.T / sqrt(d)) @ V``
@@ -200,8 +263,27 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
     +inf). A head one of whose scores q . k overflows f32 to +inf gets a NaN row (the
     definition: the V row of that position). The numerator sum(p~ v), p~ = exp(s - max s) <=
     1, is summed in f32 before the division by sum(p~): where it overflows the result is +-inf
-    although the quotient would be finite."""
-    b, kvh, cap, d = _check_caches(k_cache, v_cache)
+    although the quotient would be finite.
+    MXFP8 caches (`k_scale` and `v_scale` given; attn_decode_mxfp8.hip): `k_cache` and
+    `v_cache` are the uint8 e4m3fn codes [B, kv_heads, capacity, d], 16-byte aligned, the
+    scales the uint8 E8M0 bytes [B, kv_heads, capacity, d // 32], block j of a row being
+    elements [32 j, 32 j + 32); all contiguous, d 64 or 128 - 33/64 of the bf16 cache's bytes.
+    Dequantization is ``code * 2**(byte - 127)`` rounded to bf16 to nearest even, which is
+    exact except where the product falls between bf16 subnormals (a subnormal code at a byte
+    of 3 or less). The result is that of this op on the dequantized cache - f32 scores,
+    online softmax per 32 positions, P rounded to bf16, the same chunks and combine - and as
+    bit-invariant to batch, slot, capacity and `max_len`; bit equality with the bf16 kernel
+    is not promised, because K's d sit in other k slots of the MFMA. The GPU kernel
+    dequantizes codes in registers into the bf16 MFMA's operands, K from 16-byte and V from 8-
+    (d = 64: 4-) byte loads, and loads neither codes nor scale bytes at or behind lens[b].
+    The quantizers write scale bytes in [1, 247]; a byte of 255 or a NaN code (0x7F / 0xFF)
+    inside the valid prefix makes the rows of that (sequence, KV head) NaN - in K all of
+    each row, in V the d of the code or the 32 d of the byte's block - and leaves every
+    other row its bits; a byte of 0 is outside the contract (an unspecified value, no
+    out-of-bounds access). CPU: the valid prefix dequantized, then the definition in f32.
+    bf16 caches with a scale, uint8 caches without both, scales of another shape, dtype,
+    device or layout and d = 32 are ValueErrors before any launch."""
+    b, kvh, cap, d = _check_caches(k_cache, v_cache, k_scale, v_scale)
     dev = k_cache.device
     _check_out_dtype(out_dtype)
     _check_rows(q, "q", dev, q.dim() == 3 and q.shape[0] == b and q.shape[2] == d and q.shape[1] >= 1,
@@ -221,8 +303,11 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
             n = min(max(n, 0), cap)
             if n == 0:
                 continue
-            kk = k_cache[i, :, :n].float().repeat_interleave(g, dim=0)  # [heads, n, d]
-            vv = v_cache[i, :, :n].float().repeat_interleave(g, dim=0)
+            if k_scale is None:
+                kk, vv = k_cache[i, :, :n].float(), v_cache[i, :, :n].float()
+            else:
+                kk, vv = _mxfp8_rows(k_cache[i, :, :n], k_scale[i, :, :n]), _mxfp8_rows(v_cache[i, :, :n], v_scale[i, :, :n])
+            kk, vv = kk.repeat_interleave(g, dim=0), vv.repeat_interleave(g, dim=0)  # [heads, n, d]
             s = torch.einsum("hd,hnd->hn", q[i].float(), kk) / d ** 0.5
             y[i] = torch.einsum("hn,hnd->hd", torch.softmax(s, -1), vv)
         return y.view(b, heads * d).to(out_dtype)
@@ -232,6 +317,11 @@ def attn_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, l
         raise ValueError("the batch is too large for one launch")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     y = torch.empty(b, heads * d, dtype=out_dtype, device=dev)
+    if k_scale is not None:
+        _core.attn_decode_mxfp8(q.data_ptr(), k_cache.data_ptr(), k_scale.data_ptr(), v_cache.data_ptr(),
+                                v_scale.data_ptr(), lens.data_ptr(), b, heads, kvh, d, cap, max_len, ws.data_ptr(),
+                                nbytes, y.data_ptr(), out_dtype == torch.bfloat16, _stream())
+        return y
     _core.attn_decode(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), lens.data_ptr(), b, heads, kvh, d, cap,
                       max_len, ws.data_ptr(), nbytes, y.data_ptr(), out_dtype == torch.bfloat16, _stream())
     return y
