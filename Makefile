@@ -6,6 +6,7 @@
 #   make sanitize-mxfp6 -> build/tests/mxfp6_selftest_asan (the MXFP6 host codec under ASan + UBSan), and runs it
 #   make sanitize-attn  -> build/tests/attn_decode_selftest_asan (the attention's launch sizing under ASan + UBSan), and runs it
 #   make sanitize-attn-prefill -> build/tests/attn_prefill_selftest_asan (the prefill attention's launch sizing, the same way), and runs it
+#   make sanitize-attn-prefill-mxfp8 -> build/tests/attn_prefill_mxfp8_selftest_asan (the MXFP8 prefill attention's and rope's index arithmetic, the same way), and runs it
 #
 # The extension links the HIP runtime and RCCL that PyTorch-ROCm ships, so one
 # process never holds two HIP runtimes (torch is imported before _core).
@@ -132,7 +133,17 @@ $(BUILD)/tests/attn_prefill_selftest_asan: csrc/tests/attn_prefill_selftest.cc c
 sanitize-attn-prefill: $(BUILD)/tests/attn_prefill_selftest_asan
 	$(BUILD)/tests/attn_prefill_selftest_asan
 
+# The same for the MXFP8 prefill attention and many-token rope: the code and scale-byte
+# loads, the LDS stash and the cache stores as well, over exact-size buffers.
+$(BUILD)/tests/attn_prefill_mxfp8_selftest_asan: csrc/tests/attn_prefill_mxfp8_selftest.cc csrc/kernels/attn_plan.h
+	@mkdir -p $(dir $@)
+	$(CXX) -O1 -g -std=c++17 -Icsrc -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	  -static-libasan -static-libubsan -o $@ csrc/tests/attn_prefill_mxfp8_selftest.cc
+
+sanitize-attn-prefill-mxfp8: $(BUILD)/tests/attn_prefill_mxfp8_selftest_asan
+	$(BUILD)/tests/attn_prefill_mxfp8_selftest_asan
+
 clean:
 	rm -rf $(BUILD) $(PKG)/_core*.so bin/diskspeed bin/h2dbench bin/contention
 
-.PHONY: all tools sanitize sanitize-mxfp6 sanitize-attn sanitize-attn-prefill clean
+.PHONY: all tools sanitize sanitize-mxfp6 sanitize-attn sanitize-attn-prefill sanitize-attn-prefill-mxfp8 clean

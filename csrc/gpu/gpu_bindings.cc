@@ -832,6 +832,39 @@ void register_gpu_bindings(PyObject* module) {
   }, py::arg("q"), py::arg("ldq"), py::arg("k"), py::arg("ldk"), py::arg("v"), py::arg("ldv"), py::arg("start"),
      py::arg("cos"), py::arg("sin"), py::arg("b"), py::arg("s"), py::arg("heads"), py::arg("kv_heads"), py::arg("d"),
      py::arg("capacity"), py::arg("q_out"), py::arg("k_cache"), py::arg("v_cache"), py::arg("stream") = 0);
+  // the same two against an MXFP8 KV cache: contiguous codes and E8M0 scale bytes (kernels/attn_prefill_mxfp8.hip)
+  m.def("attn_prefill_mxfp8", [](uint64_t q, uint64_t k_codes, uint64_t k_scales, uint64_t v_codes, uint64_t v_scales,
+                                 uint64_t start, int64_t b, int64_t s, int64_t heads, int64_t kv_heads, int64_t d,
+                                 int64_t t, uint64_t y, bool y_bf16, uint64_t stream) {
+    if (!kern::attn_prefill_mxfp8_plan(b, s, heads, kv_heads, d, t).ok)
+      throw std::invalid_argument("attn_prefill_mxfp8: a shape the kernel does not serve");
+    check(kern::attn_prefill_mxfp8(reinterpret_cast<const uint16_t*>(q), reinterpret_cast<const uint8_t*>(k_codes),
+                                   reinterpret_cast<const uint8_t*>(k_scales), reinterpret_cast<const uint8_t*>(v_codes),
+                                   reinterpret_cast<const uint8_t*>(v_scales), reinterpret_cast<const int32_t*>(start), b,
+                                   s, heads, kv_heads, d, t, reinterpret_cast<void*>(y), y_bf16, as_stream(stream)),
+          "attn_prefill_mxfp8");
+  }, py::arg("q"), py::arg("k_codes"), py::arg("k_scales"), py::arg("v_codes"), py::arg("v_scales"), py::arg("start"),
+     py::arg("b"), py::arg("s"), py::arg("heads"), py::arg("kv_heads"), py::arg("d"), py::arg("t"), py::arg("y"),
+     py::arg("y_bf16"), py::arg("stream") = 0);
+  m.def("attn_rope_append_seq_mxfp8", [](uint64_t q, int64_t ldq, uint64_t k, int64_t ldk, uint64_t v, int64_t ldv,
+                                         uint64_t start, uint64_t cos, uint64_t sin, int64_t b, int64_t s,
+                                         int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity, uint64_t q_out,
+                                         uint64_t k_codes, uint64_t k_scales, uint64_t v_codes, uint64_t v_scales,
+                                         uint64_t stream) {
+    if (!kern::attn_rope_seq_mxfp8_plan(b, s, heads, kv_heads, d, capacity, ldq, ldk, ldv).ok)
+      throw std::invalid_argument("attn_rope_append_seq_mxfp8: a shape or stride the kernel does not serve");
+    check(kern::attn_rope_append_seq_mxfp8(
+              reinterpret_cast<const uint16_t*>(q), ldq, reinterpret_cast<const uint16_t*>(k), ldk,
+              reinterpret_cast<const uint16_t*>(v), ldv, reinterpret_cast<const int32_t*>(start),
+              reinterpret_cast<const float*>(cos), reinterpret_cast<const float*>(sin), b, s, heads, kv_heads, d,
+              capacity, reinterpret_cast<uint16_t*>(q_out), reinterpret_cast<uint8_t*>(k_codes),
+              reinterpret_cast<uint8_t*>(k_scales), reinterpret_cast<uint8_t*>(v_codes),
+              reinterpret_cast<uint8_t*>(v_scales), as_stream(stream)),
+          "attn_rope_append_seq_mxfp8");
+  }, py::arg("q"), py::arg("ldq"), py::arg("k"), py::arg("ldk"), py::arg("v"), py::arg("ldv"), py::arg("start"),
+     py::arg("cos"), py::arg("sin"), py::arg("b"), py::arg("s"), py::arg("heads"), py::arg("kv_heads"), py::arg("d"),
+     py::arg("capacity"), py::arg("q_out"), py::arg("k_codes"), py::arg("k_scales"), py::arg("v_codes"),
+     py::arg("v_scales"), py::arg("stream") = 0);
   // (BQ, BK): query rows of a workgroup, positions of a K / V tile
   m.def("attn_prefill_tiles", []() { return std::make_pair(kern::kAttnPrefillBQ, kern::kAttnPrefillBK); });
 

@@ -56,15 +56,6 @@ constexpr int kStep = 32;  // positions of one wave step
 constexpr int kStepsPerWave = kC / (kStep * kWaves);
 static_assert(kC == kStep * kWaves * kStepsPerWave, "a chunk is a whole number of steps per wave");
 
-// The f32 whose exponent field is the E8M0 byte `e`: 2^(e - 127), and the instruction reads nothing else of it.
-__device__ __forceinline__ float e8m0_scale(uint32_t e) { return __uint_as_float((e & 0xFFu) << 23); }
-
-// Four codes (one word) times `s` as four bf16 in two operand words.
-__device__ __forceinline__ void dequant4(uint32_t codes, float s, uint32_t& w0, uint32_t& w1) {
-  w0 = fp8x2_to_bf16x2<false>(codes, s);
-  w1 = fp8x2_to_bf16x2<true>(codes, s);
-}
-
 // ---------------------------------------------------------------- attn_decode_mxfp8
 template <int D>
 __global__ void __launch_bounds__(64 * kWaves)

@@ -1,8 +1,8 @@
 // Host-side sizing of the single-token attention and rope (attn_decode.hip; on
 // an MXFP8 cache attn_decode_mxfp8.hip) and of the causal prefill / extend
-// attention and many-token rope (attn_prefill.hip): the shape and stride checks, the tile constants, the grids and the workspace as
+// attention and many-token rope (attn_prefill.hip; on an MXFP8 cache attn_prefill_mxfp8.hip): the shape and stride checks, the tile constants, the grids and the workspace as
 // plain integer arithmetic, with no HIP in it, so that stand-alone programs can run it
-// under a sanitizer (csrc/tests/attn_decode_selftest.cc, attn_prefill_selftest.cc).
+// under a sanitizer (csrc/tests/attn_decode_selftest.cc, attn_prefill_selftest.cc, attn_prefill_mxfp8_selftest.cc).
 #pragma once
 
 #include <cstdint>
@@ -173,6 +173,42 @@ inline AttnRopeSeqPlan attn_rope_seq_plan(int64_t B, int64_t S, int64_t heads, i
   p.threads = B * S * (heads + 2 * kv_heads) * (d / 16);  // <= 2^31 2^17 2^3 = 2^51
   p.blocks = (p.threads + kAttnPrefillThreads - 1) / kAttnPrefillThreads;
   if (p.blocks > 0x7FFFFFFF) return p;
+  p.ok = true;
+  return p;
+}
+
+// ---- the same two against the MXFP8 KV cache (attn_prefill_mxfp8.hip).
+
+// attn_prefill_plan for contiguous codes [B, kv_heads, T, d] and scale bytes [B, kv_heads, T, d / 32]: the
+// same grid. The strides checked are the contiguous ones, so a sequence's codes stay within
+// kAttnPrefillMaxStride bytes and the last code's offset, B kv_heads T d - 1 <= 2^20 2^40, within int64.
+inline AttnPrefillPlan attn_prefill_mxfp8_plan(int64_t B, int64_t S, int64_t heads, int64_t kv_heads, int64_t d,
+                                               int64_t T) {
+  if (!attn_mxfp8_d_ok(d) || kv_heads < 1 || kv_heads > 65535 || T < 1 || T > kAttnMaxPositions)
+    return AttnPrefillPlan();
+  const int64_t st[3] = {kv_heads * T * d, T * d, d};  // <= 2^16 2^20 2^7
+  return attn_prefill_plan(B, S, heads, kv_heads, d, T, st, st);
+}
+
+// The many-token MXFP8 rope and append: workgroup (n, y) takes items [y * kAttnRopeMxThreads, ...) - the items
+// of attn_rope_mxfp8_plan - of row n = b * S + i, so a row's position is one value for the whole workgroup.
+struct AttnRopeSeqMxPlan {
+  bool ok = false;
+  int64_t rows = 0;  // B * S: grid.x
+  int items = 0;     // (heads + 2 kv_heads) * (d / 16)
+  int grid_y = 0;    // workgroups of a row
+};
+
+inline AttnRopeSeqMxPlan attn_rope_seq_mxfp8_plan(int64_t B, int64_t S, int64_t heads, int64_t kv_heads, int64_t d,
+                                                  int64_t capacity, int64_t ldq, int64_t ldk, int64_t ldv) {
+  AttnRopeSeqMxPlan p;
+  if (!attn_mxfp8_d_ok(d) || B < 1 || B > kAttnPrefillMaxBatch || S < 1 || S > kAttnMaxPositions) return p;
+  if (B * S > 0x7FFFFFFF) return p;  // grid.x
+  if (!attn_rope_rows_ok(B, heads, kv_heads, d, capacity, ldq, ldk, ldv)) return p;
+  if (ldq % 8 || ldk % 8 || ldv % 8) return p;  // 16-byte loads
+  p.rows = B * S;
+  p.items = int((heads + 2 * kv_heads) * (d / 16));  // <= 3 * 65535 * 8
+  p.grid_y = (p.items + kAttnRopeMxThreads - 1) / kAttnRopeMxThreads;  // <= 6144
   p.ok = true;
   return p;
 }

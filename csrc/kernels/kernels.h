@@ -433,5 +433,37 @@ hipError_t attn_rope_append_seq(const uint16_t* q, int64_t ldq, const uint16_t* 
                                 int64_t S, int64_t heads, int64_t kv_heads, int64_t d, int64_t capacity,
                                 uint16_t* q_out, uint16_t* k_cache, uint16_t* v_cache, hipStream_t s);
 
+// ---- attn_prefill_mxfp8.hip: the same two against an MXFP8 KV cache (the format of attn_decode_mxfp8.hip
+// above): codes uint8 [B, kv_heads, T, d] on 16-byte-aligned bases and E8M0 scale bytes uint8 [B, kv_heads, T,
+// d / 32], all contiguous - no strides - and d 64 or 128; every other limit is attn_prefill's.
+//
+// attn_prefill_mxfp8, ONE launch: attn_prefill's decomposition, grid, tiles, masking and epilogue; a K / V
+// tile is loaded as codes (16 a lane and load) with its scale bytes and dequantized once per workgroup on the
+// way from registers into LDS (fp8x2_to_bf16x2), so LDS holds the bf16 tile attn_prefill holds.
+//   Result: for codes and scale bytes whose dequantization code * 2^(byte - 127) is exact in bf16 - everything
+// the quantizers write; the exception is a subnormal code at a byte of 3 or less - the BITS of attn_prefill on
+// the dequantized bf16 cache, f32 and bf16. attn_prefill's invariance (batch, slot, S, start, T, split of the
+// tokens into passes) and its non-finite behaviour carry over: a NaN code (0x7F / 0xFF) or a scale byte of 255
+// inside a sequence's valid positions acts as the NaN values it dequantizes to (a byte of 255: the 32 d of its
+// block). A scale byte of 0 is outside the contract: the value is unspecified, and no access leaves the tensors.
+// Neither codes nor scale bytes at or behind min(start[b] + S, T) are ever loaded.
+//
+// attn_rope_append_seq_mxfp8, ONE launch: attn_rope_append_mxfp8 for S tokens a sequence, token i of sequence
+// b at position start[b] + i (start int32 [B] on the device, or null for zero); q, k, v, cos, sin and q_out as
+// in attn_rope_append_seq. q_out has attn_rope_append_seq's bits; the four cache tensors receive exactly the
+// bytes S successive attn_rope_append_mxfp8 launches write - mxfp8::quantize_host of the rotated, bf16-rounded
+// k rows and of the v rows - and no other byte changes. A position outside [0, capacity) writes nothing to the
+// four tensors and a zero q_out row. One workgroup per (row b * S + i, kAttnRopeMxThreads items), B * S at
+// most 2^31 - 1. Anything else, for both: hipErrorInvalidValue, before any launch.
+hipError_t attn_prefill_mxfp8(const uint16_t* q, const uint8_t* k_codes, const uint8_t* k_scales,
+                              const uint8_t* v_codes, const uint8_t* v_scales, const int32_t* start, int64_t B,
+                              int64_t S, int64_t heads, int64_t kv_heads, int64_t d, int64_t T, void* y, bool y_bf16,
+                              hipStream_t s);
+hipError_t attn_rope_append_seq_mxfp8(const uint16_t* q, int64_t ldq, const uint16_t* k, int64_t ldk,
+                                      const uint16_t* v, int64_t ldv, const int32_t* start, const float* cos,
+                                      const float* sin, int64_t B, int64_t S, int64_t heads, int64_t kv_heads,
+                                      int64_t d, int64_t capacity, uint16_t* q_out, uint8_t* k_codes,
+                                      uint8_t* k_scales, uint8_t* v_codes, uint8_t* v_scales, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dissem

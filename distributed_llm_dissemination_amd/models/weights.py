@@ -443,27 +443,34 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
     repeat_interleave of K and V. Without a `cache`, a transient [batch, kv_heads, seq,
     head_dim] pair with its rotary tables is allocated for the call. Any other `attn`
     raises ValueError.
-    `extend=True` (needs `cache` and `attn="mfma"`): the seq tokens of sequence b go to
+    `extend=True` (needs `cache` and `attn="mfma"` or `attn="mfma_mxfp8"`): the seq tokens of sequence b go to
     positions [lens[b], lens[b] + seq) of a cache that already holds lens[b] tokens and
     attend to all of them - chunked prefill and multi-token extend. `cache.lens` advances
     by seq on the device and `cache.max_len` by seq; ValueError when max_len + seq exceeds
     the capacity. Without `extend` a pass with a cache writes positions [0, seq) and sets
     lens = seq, as above.
-    An MXFP8 `cache` (``KVCache.allocate(..., kv_format="mxfp8")``) is prefilled on the
-    default attention route alone: the rotated k, and v, of positions [0, seq) are quantized
-    into it with ``ops.mxfp8_quantize_rows`` - the bytes a sequence of `decoder_step`s would
-    have written - while the pass attends on the fresh bf16 k and v, so its result is that
-    without a cache. `attn="mfma"` or `extend=True` with such a cache raises ValueError: a
-    prefill kernel that reads this format and a ``rope_append_seq`` that writes it do not
-    exist yet."""
+    An MXFP8 `cache` (``KVCache.allocate(..., kv_format="mxfp8")``) has two routes. On the
+    default attention route the rotated k, and v, of positions [0, seq) are quantized into it
+    with ``ops.mxfp8_quantize_rows`` - the bytes a sequence of `decoder_step`s would have
+    written - while the pass attends on the fresh bf16 k and v, so its result is that without
+    a cache; there is no extend on this route. `attn="mfma_mxfp8"` (opt-in; needs an MXFP8
+    `cache`, ValueError otherwise, for a bf16 cache too) is `attn="mfma"` for that format:
+    ``ops.rope_append_seq(..., k_scale=, v_scale=)`` rotates, quantizes and appends - the same
+    bytes - and ``ops.attn_prefill(..., k_scale=, v_scale=)`` attends on the cache's codes,
+    with `extend`, `cache.lens` and `cache.max_len` as above: prefill, chunked prefill and
+    multi-token extend. Its result is that of attention over the QUANTIZED cache - what every
+    later `decoder_step` sees - and not the default route's on the fresh bf16 k and v.
+    `attn="mfma"` with such a cache still raises ValueError: name the format's route."""
     if act not in (None, "mxfp8"):
         raise ValueError(f"act must be None or 'mxfp8', got {act!r}")
-    if attn not in (None, "mfma"):
-        raise ValueError(f"attn must be None or 'mfma', got {attn!r}")
-    if extend and (cache is None or attn != "mfma"):
-        raise ValueError("extend=True needs a cache and attn='mfma'")
+    if attn not in (None, "mfma", "mfma_mxfp8"):
+        raise ValueError(f"attn must be None, 'mfma' or 'mfma_mxfp8', got {attn!r}")
+    if extend and (cache is None or attn is None):
+        raise ValueError("extend=True needs a cache and attn='mfma' or 'mfma_mxfp8'")
     if attn == "mfma" and cache is not None and cache.k_scale is not None:
-        raise ValueError("attn='mfma' and extend=True do not serve an MXFP8 cache: prefill it on the default route")
+        raise ValueError("attn='mfma' does not serve an MXFP8 cache: use attn='mfma_mxfp8' or the default route")
+    if attn == "mfma_mxfp8" and (cache is None or cache.k_scale is None):
+        raise ValueError("attn='mfma_mxfp8' needs an MXFP8 cache (KVCache.allocate(..., kv_format='mxfp8'))")
     b, s, _ = x.shape
     hd, nh, nkv = spec.head_dim, spec.heads, spec.kv_heads
     if cache is not None:
@@ -474,7 +481,7 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
             raise ValueError(f"{cache.max_len} + {s} positions do not fit a cache of {cache.capacity}")
     h = _rms_norm(x, _dense(p["input_layernorm"]), spec.eps)
     q, k, v = _qkv(h, p, fuse, tiled, act)
-    if attn == "mfma":
+    if attn is not None:
         from ..ops import attn_prefill, rope_append_seq
 
         if cache is None:
@@ -483,9 +490,10 @@ def decoder_forward(x: torch.Tensor, p: Dict[str, Param], spec: DecoderSpec, fus
             cos, sin = _rope_tables(s, hd, spec.rope_theta, x.device)
         else:
             kc, vc, cos, sin = cache.k, cache.v, cache.cos, cache.sin
+        scales = dict(k_scale=cache.k_scale, v_scale=cache.v_scale) if attn == "mfma_mxfp8" else {}
         start = cache.lens if extend else None
-        q = rope_append_seq(q, k, v, cos, sin, kc, vc, start)
-        a = attn_prefill(q, kc, vc, start, out_dtype=x.dtype)
+        q = rope_append_seq(q, k, v, cos, sin, kc, vc, start, **scales)
+        a = attn_prefill(q, kc, vc, start, out_dtype=x.dtype, **scales)
         if extend:
             cache.lens.add_(s)
             cache.max_len += s

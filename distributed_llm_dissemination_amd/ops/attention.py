@@ -1,4 +1,5 @@
-"""The attention ops against a KV cache in HBM (csrc/kernels/attn_decode.hip, attn_prefill.hip) and their
+"""The attention ops against a KV cache in HBM (csrc/kernels/attn_decode.hip, attn_prefill.hip and their
+MXFP8 files) and their
 host references, under the conventions of kernels.py (current stream, every check before any launch).
 
     # one decode step's attention: caches bf16 [B, kv_heads, capacity, d], lens / pos int32 [B] on the device
@@ -11,6 +12,9 @@ host references, under the conventions of kernels.py (current stream, every chec
     # S tokens a sequence (prefill, chunked prefill, extend): q/k/v [B, S, heads or kv_heads * d], start int32 [B]
     q_rot = ops.rope_append_seq(q, k, v, cos, sin, k_cache, v_cache, start)   # positions start[b] + i
     a = ops.attn_prefill(q_rot, k_cache, v_cache, start)                      # [B, S, heads * d], causal, reads the cache
+    # the same against an MXFP8 cache (attn_prefill_mxfp8.hip): codes and scale bytes as above, contiguous
+    q_rot = ops.rope_append_seq(q, k, v, cos, sin, k_codes, v_codes, start, k_scale=k_scale, v_scale=v_scale)
+    a = ops.attn_prefill(q_rot, k_codes, v_codes, start, k_scale=k_scale, v_scale=v_scale)
 """
 
 from __future__ import annotations
@@ -341,7 +345,60 @@ def _kv_strides(t: torch.Tensor) -> Tuple[int, int, int]:
     return tuple(t.stride(i) if t.shape[i] > 1 else 0 for i in range(3))
 
 
+def _prefill_cpu(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start: Optional[torch.Tensor],
+                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The host route of attn_prefill: per sequence the definition in f32, [B, S, heads * d] f32; with scales
+    on the dequantized valid prefix."""
+    b, s, heads, d = q.shape
+    kvh, t_len = k.shape[1], k.shape[2]
+    y = torch.zeros(b, s, heads, d, dtype=torch.float32)
+    st = [0] * b if start is None else [min(max(n, 0), t_len) for n in start.tolist()]
+    g = heads // kvh
+    for i in range(b):
+        rows = min(s, t_len - st[i])  # rows whose position is below T
+        if rows <= 0:
+            continue
+        n = st[i] + rows
+        if k_scale is None:
+            kk, vv = k[i, :, :n].float(), v[i, :, :n].float()
+        else:
+            kk, vv = _mxfp8_rows(k[i, :, :n], k_scale[i, :, :n]), _mxfp8_rows(v[i, :, :n], v_scale[i, :, :n])
+        kk, vv = kk.repeat_interleave(g, dim=0), vv.repeat_interleave(g, dim=0)  # [heads, n, d]
+        sc = torch.einsum("shd,hnd->hsn", q[i, :rows].float(), kk) / d ** 0.5
+        seen = torch.arange(n)[None, :] <= (st[i] + torch.arange(rows))[:, None]
+        p = torch.softmax(sc.masked_fill(~seen, float("-inf")), -1)
+        y[i, :rows] = torch.einsum("hsn,hnd->shd", p, vv)
+    return y.view(b, s, heads * d)
+
+
+def _attn_prefill_mxfp8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start: Optional[torch.Tensor],
+                        k_scale: Optional[torch.Tensor], v_scale: Optional[torch.Tensor],
+                        out_dtype: torch.dtype) -> torch.Tensor:
+    """attn_prefill against MXFP8 caches: every check, then the host route or attn_prefill_mxfp8.hip."""
+    b, kvh, t_len, d = _check_caches(k, v, k_scale, v_scale)
+    dev = k.device
+    _check_rows(q, "q", dev, q.dim() == 4 and q.shape[0] == b and q.shape[3] == d and q.shape[1] >= 1
+                and q.shape[2] >= 1, f"[{b}, S, heads, {d}]")
+    s, heads = q.shape[1], q.shape[2]
+    _check_heads(heads, kvh)
+    if s > _ATTN_MAX_CAPACITY:
+        raise ValueError(f"S must be at most {_ATTN_MAX_CAPACITY}, got {s}")
+    if start is not None:
+        _check_index(start, "start", b, dev)
+    if dev.type != "cuda":
+        return _prefill_cpu(q, k, v, start, k_scale, v_scale).to(out_dtype)
+    if b > (1 << 20) or b * heads * -(-s // _core.attn_prefill_tiles()[0]) > 0x7FFFFFFF:
+        raise ValueError("the batch is too large for one launch")
+    q = _aligned_q(q)
+    y = torch.empty(b, s, heads * d, dtype=out_dtype, device=dev)
+    _core.attn_prefill_mxfp8(q.data_ptr(), k.data_ptr(), k_scale.data_ptr(), v.data_ptr(), v_scale.data_ptr(),
+                             0 if start is None else start.data_ptr(), b, s, heads, kvh, d, t_len, y.data_ptr(),
+                             out_dtype == torch.bfloat16, _stream())
+    return y
+
+
 def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start: Optional[torch.Tensor] = None, *,
+                 k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                  out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
     """Causal grouped-query attention of S new tokens per sequence against K and V that already
     hold them (a prefill, or the extend of a cache by S tokens): row (b, i) of the [B, S, heads *
@@ -373,8 +430,25 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start: Optio
     a non-finite V element at position j makes that d non-finite in the rows at and behind j,
     and NaN in the rows fewer than 63 positions BEFORE j whose wave still visits j's 32
     positions - there it meets a weight of exactly 0 (the definition: no effect). Every other
-    row, head and sequence keeps its bits."""
+    row, head and sequence keeps its bits.
+    MXFP8 caches (`k_scale` and `v_scale` given; attn_prefill_mxfp8.hip): `k` and `v` are the
+    uint8 e4m3fn codes [B, kv_heads, T, d], 16-byte aligned, the scales the uint8 E8M0 bytes
+    [B, kv_heads, T, d // 32] of `attn_decode`'s format; all contiguous (no strided views), d
+    64 or 128. GPU: the same decomposition; a tile's codes, 16 a lane and load, and scale
+    bytes are dequantized once per workgroup on the way from registers into LDS, which then
+    holds the bf16 tile the bf16 kernel holds. For codes and scale bytes whose dequantization
+    ``code * 2**(byte - 127)`` is exact in bf16 - everything the quantizers write - the result
+    has the bits of this op on the dequantized bf16 cache, in f32 and in bf16, and with them
+    its invariance (batch, slot, S, start, T, split into passes) and its non-finite
+    behaviour: a NaN code (0x7F / 0xFF) or a scale byte of 255 inside the valid positions
+    acts as the NaN values it dequantizes to. A scale byte of 0 is outside the contract (an
+    unspecified value, no out-of-bounds access). Neither codes nor scale bytes at or behind
+    min(start[b] + S, T) are loaded. CPU: the valid prefix dequantized, then the definition in
+    f32. bf16 tensors with a scale, uint8 tensors without both, scales of another shape,
+    dtype, device or layout and d = 32 are ValueErrors before any launch."""
     _check_out_dtype(out_dtype)
+    if k_scale is not None or v_scale is not None:
+        return _attn_prefill_mxfp8(q, k, v, start, k_scale, v_scale, out_dtype)
     for name, t in (("q", q), ("k", k), ("v", v)):
         if t.dtype != torch.bfloat16:
             raise ValueError(f"{name} must be {torch.bfloat16}, got {t.dtype}")
@@ -397,21 +471,7 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start: Optio
     if start is not None:
         _check_index(start, "start", b, dev)
     if dev.type != "cuda":
-        y = torch.zeros(b, s, heads, d, dtype=torch.float32)
-        st = [0] * b if start is None else [min(max(n, 0), t_len) for n in start.tolist()]
-        g = heads // kvh
-        for i in range(b):
-            rows = min(s, t_len - st[i])  # rows whose position is below T
-            if rows <= 0:
-                continue
-            n = st[i] + rows
-            kk = k[i, :, :n].float().repeat_interleave(g, dim=0)  # [heads, n, d]
-            vv = v[i, :, :n].float().repeat_interleave(g, dim=0)
-            sc = torch.einsum("shd,hnd->hsn", q[i, :rows].float(), kk) / d ** 0.5
-            seen = torch.arange(n)[None, :] <= (st[i] + torch.arange(rows))[:, None]
-            p = torch.softmax(sc.masked_fill(~seen, float("-inf")), -1)
-            y[i, :rows] = torch.einsum("hsn,hnd->shd", p, vv)
-        return y.view(b, s, heads * d).to(out_dtype)
+        return _prefill_cpu(q, k, v, start).to(out_dtype)
     if b > (1 << 20) or b * heads * -(-s // _core.attn_prefill_tiles()[0]) > 0x7FFFFFFF:
         raise ValueError("the batch is too large for one launch")
     q, k, v = _aligned_q(q), _kv_view(k), _kv_view(v)
@@ -423,7 +483,8 @@ def attn_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, start: Optio
 
 
 def rope_append_seq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
-                    k_cache: torch.Tensor, v_cache: torch.Tensor, start: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    k_cache: torch.Tensor, v_cache: torch.Tensor, start: Optional[torch.Tensor] = None, *,
+                    k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """`rope_append` for S tokens per sequence in one launch: the rotary embedding of q and k at
     positions start[b] + i, fused with the cache append.
 
@@ -439,8 +500,17 @@ def rope_append_seq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torc
     capacity) writes nothing to the caches and gives a zero q row.
     GPU (attn_prefill.hip): one launch on the current stream, 16-byte loads and stores - a
     thread rotates 8 d of the lower half with their partners of the upper half - and no
-    synchronization (`start` is never read on the host). CPU: plain torch."""
-    b, kvh, cap, d = _check_caches(k_cache, v_cache)
+    synchronization (`start` is never read on the host). CPU: plain torch.
+    MXFP8 caches (`k_scale` and `v_scale` given; attn_prefill_mxfp8.hip): `k_cache` and
+    `v_cache` are the uint8 codes and the scales the uint8 E8M0 bytes of `rope_append`'s
+    format, d 64 or 128. The returned q has the bits of the bf16 route; the four tensors
+    receive exactly the bytes S successive ``rope_append(..., k_scale=, v_scale=)`` calls
+    write - the host codec's of the rows the bf16 route writes - and no other byte changes; a
+    position outside [0, capacity) writes nothing to them. GPU: still one launch - `rope_append`'s
+    thread map and quantizer, one workgroup per (token, 256 items of its heads), B * S below
+    2**31. bf16 caches with a scale, uint8 caches without both, scales of another shape,
+    dtype, device or layout and d = 32 are ValueErrors before any launch."""
+    b, kvh, cap, d = _check_caches(k_cache, v_cache, k_scale, v_scale)
     dev = k_cache.device
     if start is not None:
         _check_index(start, "start", b, dev)
@@ -455,8 +525,20 @@ def rope_append_seq(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torc
                   _rows_seq(v, "v", b, s, kvh * d, dev))
     if dev.type != "cuda":
         st = torch.zeros(b, dtype=torch.long) if start is None else start.long()
-        return _rope_cpu(q2, k2, v2, cos, sin, k_cache, v_cache, st[:, None] + torch.arange(s)[None, :], heads)
+        return _rope_cpu(q2, k2, v2, cos, sin, k_cache, v_cache, st[:, None] + torch.arange(s)[None, :], heads,
+                         k_scale, v_scale)
     q_out = torch.empty(b, s, heads, d, dtype=torch.bfloat16, device=dev)
+    if k_scale is not None:
+        if cos.data_ptr() % 16 or sin.data_ptr() % 16:
+            raise ValueError("cos and sin must be 16-byte aligned")
+        if b * s > 0x7FFFFFFF:
+            raise ValueError("too many tokens for one launch")
+        _core.attn_rope_append_seq_mxfp8(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(),
+                                         v2.stride(0), 0 if start is None else start.data_ptr(), cos.data_ptr(),
+                                         sin.data_ptr(), b, s, heads, kvh, d, cap, q_out.data_ptr(),
+                                         k_cache.data_ptr(), k_scale.data_ptr(), v_cache.data_ptr(),
+                                         v_scale.data_ptr(), _stream())
+        return q_out
     _core.attn_rope_append_seq(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(), v2.stride(0),
                                0 if start is None else start.data_ptr(), cos.data_ptr(), sin.data_ptr(), b, s, heads,
                                kvh, d, cap, q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _stream())
